@@ -9,8 +9,14 @@ With N > 1 ranks (one process per GPU, torch.distributed over RCCL) each rank
 renders its own 64 views (weak scaling) and the shared vertex gradient (V x 3
 f32) is all-reduced every step — the only data exchange the path has.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 Prints ONE JSON line on rank 0 (contract in the task statement / DESIGN.md §Measurement).
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`).
+`--dump-outputs DIR` also writes what the last timed step computed (DIR/<name>.npy, see dump_outputs).
+`--full` adds everything else the line can carry, each measured in a run of its own after the timed
+steps: the graph-vs-eager gradient check, per-kernel HIP-event times and the rooflines built on them,
+the fragment pass, the C3 / C5 / soft secondary steps and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -157,6 +163,31 @@ def path_bytes_per_frame(H, W, F, tex_texels, views, covered):
     return 20 * H * W + 20 * covered / views + 108 * F + 12 * tex_texels / views
 
 
+DUMP_MAX_ELEMS = 2 * 1024 * 1024  # per array: 8 MB of float32, so the six arrays stay under 64 MB in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write each named tensor as <path>/<name>.npy in float32. An array of more than
+    DUMP_MAX_ELEMS elements is written as a fixed sample of that many of its (flattened) elements: the
+    sorted indices drawn by a generator seeded with 0, the same for every array of one size and for every
+    run, so two builds' dumps compare element for element."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    picks = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        if n > DUMP_MAX_ELEMS:
+            if n not in picks:
+                g = torch.Generator().manual_seed(0)
+                picks[n] = torch.randint(n, (DUMP_MAX_ELEMS,), generator=g).sort().values
+            a = flat[picks[n].to(flat.device)].float().cpu().numpy()
+        else:
+            a = t.detach().float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -165,6 +196,14 @@ def main():
     ap.add_argument("--views", type=int, default=64, help="views per GPU")
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--mesh", default="cow")
+    ap.add_argument("--full", action="store_true",
+                    help="render mode: after the timed steps also run the graph-vs-eager check, the per-kernel "
+                         "timing and rooflines, the fragment pass, the C3 / C5 / soft steps and the CPU baseline "
+                         "(each can be dropped with its --no-... option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="render mode: after the timed steps write the last timed step's outputs (rank 0's depth, "
+                         "silhouette, rgb and the gradients of verts, R, t) as DIR/<name>.npy, float32; arrays of "
+                         "more than 2M elements as a fixed seeded sample of their elements")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fragment-pass", action="store_true",
                     help="render mode: skip the fragment-pass measurement that follows the headline step")
@@ -240,9 +279,13 @@ def main():
     gS = (torch.rand(nv, H, W, generator=gen) * 2 - 1).to(dev)
     gC = (torch.rand(nv, H, W, 3, generator=gen) * 2 - 1).to(dev)
 
+    last_outs = [None]  # --eager --dump-outputs: the last eager step's images
+
     def fwd_bwd():
         depth, sil, rgb = renderer.render(bmesh, R_cv, t_cv)
         torch.autograd.backward([depth, sil, rgb], [gD, gS, gC])
+        if args.eager and args.dump_outputs:
+            last_outs[0] = (depth.detach(), sil.detach(), rgb.detach())
 
     def eager_step():
         verts.grad = None
@@ -254,10 +297,12 @@ def main():
         eager_step()
         if world > 1:
             D.allreduce_grads([verts])
-    from torch_renderer_amd.kernels import render_stats
-    _keep = renderer.render(bmesh, R_cv, t_cv)  # autograd keeps the forward workspace alive
-    wstats = render_stats()  # work counters of this rank's batch (bytes of data-dependent kernels)
-    del _keep
+    wstats = None
+    if args.full:
+        from torch_renderer_amd.kernels import render_stats
+        _keep = renderer.render(bmesh, R_cv, t_cv)  # autograd keeps the forward workspace alive
+        wstats = render_stats()  # work counters of this rank's batch (bytes of data-dependent kernels)
+        del _keep
     torch.cuda.synchronize()
 
     # One step = fwd+bwd of the rank's views (+ the shared-vertex-gradient all-reduce when N > 1).
@@ -352,10 +397,17 @@ def main():
         e = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = e.item()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step: the three images (the captured graph's
+        # static outputs, or the last eager step's) and the leaves' gradients (verts' all-reduced when N > 1)
+        torch.cuda.synchronize()
+        o_d, o_s, o_c = last_outs[0] if args.eager else outs_static
+        dump_outputs(args.dump_outputs, {"depth": o_d, "silhouette": o_s, "rgb": o_c, "grad_verts": verts.grad,
+                                         "grad_R": R_cv.grad, "grad_t": t_cv.grad})
     # the replayed graph's gradients against an eager step's: bitwise (the step is deterministic), so
     # the graph runs exactly the step's work
     graph_check = None
-    if fwd_only is not None and world == 1:
+    if args.full and fwd_only is not None and world == 1:
         torch.cuda.synchronize()
         g_graph = (verts.grad.clone(), R_cv.grad.clone(), t_cv.grad.clone())
         eager_step()
@@ -363,17 +415,19 @@ def main():
         graph_check = all(torch.equal(a, b) for a, b in zip(g_graph, (verts.grad, R_cv.grad, t_cv.grad)))
     # per-kernel device times: HIP events around every launch of a few eager steps (same kernels)
     torch.cuda.synchronize()
-    _lib.timing_enable(True)
-    for _ in range(min(args.steps, 20)):
-        eager_step()
-    torch.cuda.synchronize()
-    kt = _lib.timing_read()
-    _lib.timing_enable(False)
+    kt = {}
+    if args.full:
+        _lib.timing_enable(True)
+        for _ in range(min(args.steps, 20)):
+            eager_step()
+        torch.cuda.synchronize()
+        kt = _lib.timing_read()
+        _lib.timing_enable(False)
     # rehearsal check (MR_BENCH_REHEARSE, N ranks sharing one GPU over gloo): the all-reduced vertex
     # gradient equals rank 0's single-process fwd+bwd of ALL the ranks' views (tolerance: the per-face sums
     # are grouped by rank there)
     ar_check = None
-    if world > 1 and rehearse:
+    if args.full and world > 1 and rehearse:
         step()
         torch.cuda.synchronize()
         g_ar = verts.grad.detach().clone()
@@ -400,12 +454,12 @@ def main():
         del g_fwd, g_bwd, outs_static
     torch.cuda.synchronize()
     frag = None
-    if not args.no_fragment_pass:
+    if args.full and not args.no_fragment_pass:
         f_el, f_kt, f_cov, _ = measure_fragments(args, dev, world, rank)
         frag = fragment_pass_summary(args, f_el, f_kt, f_cov, Fn, world)
     # (one GPU only: the multi-GPU lines report the headline's scaling; a secondary workload's collective
     # must never be able to stall a scaling run)
-    secondary = {} if args.no_secondary or world > 1 else secondary_steps(args, dev, world, rank)
+    secondary = {} if not args.full or args.no_secondary or world > 1 else secondary_steps(args, dev, world, rank)
 
     if rank != 0:
         dist.destroy_process_group()
@@ -454,18 +508,20 @@ def main():
                 "frac": round(fwd_bytes / (fwd_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)} if fwd_us > 0 else None
     kernels = {k: {"launches": v[0], "avg_us": round(v[1] / max(v[0], 1) * 1e3, 2),
                    "share": round(v[1] / sum(x[1] for x in kt.values()), 3)} for k, v in kt.items()}
-    texels = d["texture_u8"].shape[0] * d["texture_u8"].shape[1] if "texture_u8" in d else 0
-    pb = path_bytes_per_frame(H, W, Fn, texels, nv, wstats["covered"])
-    path_roof = {"bytes_per_frame": int(pb), "achieved": round(value * pb / 1e9, 1), "peak": HBM_PEAK_GBS,
-                 "unit": "GB/s", "frac": round(value * pb / 1e9 / HBM_PEAK_GBS, 4)}
+    path_roof = None
+    if wstats is not None:
+        texels = d["texture_u8"].shape[0] * d["texture_u8"].shape[1] if "texture_u8" in d else 0
+        pb = path_bytes_per_frame(H, W, Fn, texels, nv, wstats["covered"])
+        path_roof = {"bytes_per_frame": int(pb), "achieved": round(value * pb / 1e9, 1), "peak": HBM_PEAK_GBS,
+                     "unit": "GB/s", "frac": round(value * pb / 1e9 / HBM_PEAK_GBS, 4)}
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(verts0, faces.cpu(), d, R_all, t_all, K, H, W, n_views=args.cpu_views, mesh=args.mesh)
     line = {
         "metric": METRIC, "value": round(value, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "launch": "eager" if args.eager else "hipgraph",
+        "launch": "eager" if args.eager else "hipgraph", "full": args.full,
         "graph_grads_equal_eager": graph_check,
         "data": (f"synthetic camera poses on the reference's {args.mesh} mesh"
                  + (" + texture (assets/cow.npz from data/cow_mesh)" if "texture_u8" in d and args.texture == "uv"
@@ -814,8 +870,8 @@ def _embedded(value, elapsed, args, kt, kt_steps, roof, workload):
 
 
 def secondary_steps(args, dev, world, rank):
-    """C3 (pose), C5 and the K = 50 soft silhouette, each at its own workload, timed in the default run
-    so that the driver's record carries them (bench.py --mode pose / c5 / soft print their full lines)."""
+    """C3 (pose), C5 and the K = 50 soft silhouette, each at its own workload, timed in the --full run
+    so that its line carries them (bench.py --mode pose / c5 / soft print their full lines)."""
     out = {}
     plans = (("pose_step", bench_pose, dict(size=512, views=64, steps=30, warmup=10)),
              ("c5_step", bench_c5, dict(size=1024, views=5, steps=60, warmup=10)),

@@ -14,7 +14,8 @@ from torch_renderer_amd.assets import load_asset, load_asset_arrays
 from torch_renderer_amd.cameras import view_batch
 from torch_renderer_amd.transforms import opencv_look_at, opencv_to_pytorch3d
 
-REF = "/root/reference/data"
+# the reference's cow (OBJ + MTL + texture) and teapot meshes, stored as fixtures (the OBJ files gzipped)
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_data")
 
 OBJ = """# test
 mtllib m.mtl
@@ -71,10 +72,15 @@ def test_assets(name, V, F):
         assert m.textures.maps_list()[0].shape == (1024, 1024, 3)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference data not present")
-def test_assets_match_reference_objs():
+def test_assets_match_reference_objs(tmp_path):
+    import gzip
+    import shutil
+
+    shutil.copytree(REF, tmp_path / "data")
     for name, rel in (("cow", "cow_mesh/cow.obj"), ("teapot", "teapot.obj")):
-        v, f, aux = load_obj(os.path.join(REF, rel))
+        with gzip.open(tmp_path / "data" / (rel + ".gz"), "rb") as src:
+            (tmp_path / "data" / rel).write_bytes(src.read())
+        v, f, aux = load_obj(tmp_path / "data" / rel)
         d = load_asset_arrays(name)
         assert np.array_equal(v.numpy(), d["verts"]) and np.array_equal(f.verts_idx.numpy(), d["faces"])
 

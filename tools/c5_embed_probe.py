@@ -34,7 +34,7 @@ def main():
     if "--after-headline" in sys.argv:  # the default line's order: headline (HIP graph), fragment pass, C3, C5
         run("alone")
         argv = sys.argv
-        sys.argv = ["bench.py", "--no-secondary", "--no-cpu-baseline", "--steps", "20", "--warmup", "5"]
+        sys.argv = ["bench.py", "--full", "--no-secondary", "--no-cpu-baseline", "--steps", "20", "--warmup", "5"]
         bench.main()
         sys.argv = argv
         gc.collect()

@@ -6,6 +6,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 TAG=$1; MODEARGS=$2; shift 2
+MODEARGS="$MODEARGS --full"  # the per-kernel times printed below are measured only with --full
 for rep in 1 2; do
   for v in base "$@"; do
     if [ "$v" = base ]; then LIB=""; else LIB="exp/$v.so"; fi
