@@ -398,6 +398,33 @@ int32_t mr_quaternion_to_matrix(const float* q, int64_t q_stride, int64_t N, flo
 int32_t mr_quaternion_to_matrix_backward(const float* q, int64_t q_stride, const float* grad_R, int64_t N,
                                          float* grad_q, void* stream);
 
+/* Mesh shape priors of a packed batch of meshes (PyTorch3D mesh_edge_loss, mesh_laplacian_smoothing(method=
+ * "uniform"), mesh_normal_consistency; deform_mesh_with_color.py:248-256, mesh_deformer.py:314-320) in one
+ * forward pass and one gathering backward. Every loss is sum(weight * term) with the weights 1 / (elements of
+ * that kind in the element's mesh * meshes) supplied by the caller:
+ *   edge       per unique edge (v0, v1):                (|v0 - v1| - target_length)^2
+ *   Laplacian  per vertex i with neighbours N(i):       |mean_{j in N(i)} v_j - v_i|   (-v_i when isolated)
+ *   normal     per pair of faces sharing edge (e0, e1), opposite vertices a, b:
+ *              1 - n0.n1 / (max(|n0|, 1e-8) max(|n1|, 1e-8)), n0 = (e1-e0) x (a-e0), n1 = -(e1-e0) x (b-e0)
+ * Topology (device, int32, built once per faces tensor by the caller): edges (E,2); nbr_ptr (V+1) / nbr (2E), the
+ * CSR of each vertex's neighbours; pairs (P,4) = e0, e1, a, b; pair_ptr (V+1) / pair_idx (4P), the CSR of each
+ * vertex's entries 4 * pair + role (role = its column in `pairs`). vert_w is (V,2): the vertex's Laplacian weight
+ * and the edge weight of its mesh. `terms` is a mask of MR_PRIOR_*; out[3] = edge, Laplacian, normal loss
+ * (device floats, 0 for a term left out). want_grad != 0 also leaves in the workspace what the backward
+ * gathers. The backward writes grad_verts (V,3) with plain stores, scaled by the device scalars g_edge / g_lap /
+ * g_norm (NULL: that loss was not differentiated); no atomics, bitwise reproducible. `terms` and the sizes must be
+ * those of the forward. mr_mesh_priors_workspace returns 0 when a size is out of range. */
+enum { MR_PRIOR_EDGE = 1, MR_PRIOR_LAPLACIAN = 2, MR_PRIOR_NORMAL = 4, MR_PRIOR_ALL = 7 };
+size_t mr_mesh_priors_workspace(int64_t V, int64_t E, int64_t P);
+int32_t mr_mesh_priors_forward(const float* verts, int64_t V, const int32_t* edges, const float* edge_w, int64_t E,
+                               const int32_t* nbr_ptr, const int32_t* nbr, const float* vert_w, const int32_t* pairs,
+                               const float* pair_w, int64_t P, float target_length, int32_t terms, int32_t want_grad,
+                               float* out, void* ws, size_t ws_bytes, void* stream);
+int32_t mr_mesh_priors_backward(const float* verts, int64_t V, const int32_t* nbr_ptr, const int32_t* nbr,
+                                const float* vert_w, const int32_t* pair_ptr, const int32_t* pair_idx, int64_t E,
+                                int64_t P, float target_length, int32_t terms, const float* g_edge, const float* g_lap,
+                                const float* g_norm, const void* fwd_ws, float* grad_verts, void* stream);
+
 /* Work counters left in `workspace` by the last mr_render_forward / mr_rasterize_meshes that used it
  * (same N, total faces, H, W, max_faces_per_bin). Synchronises `stream`; for benchmarks and tools.
  * out[0] = (tile, face) list entries, out[1] = raster work units, out[2] = non-empty 8x8 tiles,

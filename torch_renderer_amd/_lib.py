@@ -29,6 +29,7 @@ MR_OUT_ZBUF = 64  # depth output = MeshRasterizer's zbuf[..., 0] (background -1)
 MR_SREC_SLOT_SHIFT = 8  # out_flags bits 8-9: the workspace's ShadeRec slot (mr_render_reshade)
 MR_FRAG_SORTED = 1024  # mr_shade_fragments_*: empty slots follow the filled ones (this library's rasterizer)
 MR_GRAD_ROWS_CLEARED = 16  # mr_render_backward: first backward over a forward (its face totals are still clear)
+MR_PRIOR_EDGE, MR_PRIOR_LAPLACIAN, MR_PRIOR_NORMAL, MR_PRIOR_ALL = 1, 2, 4, 7  # mr_mesh_priors_*: terms mask
 
 
 class MrView(ctypes.Structure):
@@ -143,6 +144,11 @@ _SIGS = [
     ("mr_pose_loss_scale", _I32, [_VP, _I64, _I64, _I64, _VP, _VP, _VP, _VP]),
     ("mr_quaternion_to_matrix", _I32, [_VP, _I64, _I64, _VP, _VP]),
     ("mr_quaternion_to_matrix_backward", _I32, [_VP, _I64, _VP, _I64, _VP, _VP]),
+    ("mr_mesh_priors_workspace", _SZ, [_I64, _I64, _I64]),
+    ("mr_mesh_priors_forward", _I32, [_VP, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _I64, ctypes.c_float, _I32,
+                                      _I32, _VP, _VP, _SZ, _VP]),
+    ("mr_mesh_priors_backward", _I32, [_VP, _I64, _VP, _VP, _VP, _VP, _VP, _I64, _I64, ctypes.c_float, _I32, _VP,
+                                       _VP, _VP, _VP, _VP, _VP]),
     ("mr_workspace_stats", _I32, [_VP, _I64, _I64, _I32, _I32, _I32, _VP, _VP]),
     ("mr_workspace_counters", _I32, [_VP, _I64, _I64, _I32, _I32, _I32, _VP, _VP]),
     ("mr_per_view_binning", _I32, [_I64, _I64, _I32, _I32]),

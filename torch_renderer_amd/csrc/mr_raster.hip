@@ -46,6 +46,8 @@
 extern "C" {
 
 const char* mr_last_error(void) { return g_err; }
+// for the library's other translation units (mr_priors.hip): set this thread's error text, return `code`
+int mr_set_error_(int code, const char* msg) { return set_err(code, "%s", msg); }
 
 
 int32_t mr_version(void) { return 5; }

@@ -1,7 +1,7 @@
 """OBJ / MTL / PNG loading — drop-in for the ``pytorch3d.io`` calls of the reference
 (``load_objs_as_meshes`` at torch_renderer.py:8, renderer.py:75-76,
 camera_pose_optimizer.py:102, mesh_deformer.py:93; ``load_obj`` at
-camera_pose_optimizer.py:~80).
+camera_pose_optimizer.py:~80) and for ``save_obj`` (geometry only), which the deformation scripts end with.
 
 Semantics follow upstream pytorch3d/io/obj_io.py:
   * ``v``/``vt``/``vn``/``f`` records, 1-based (negative = relative) indices;
@@ -132,6 +132,29 @@ def load_obj(f, load_textures: bool = True, device="cpu"):
     dev = torch.device(device)
     faces = Faces(faces_idx.to(dev), normals_idx.to(dev), textures_idx.to(dev), materials_idx.to(dev))
     return verts_t.to(dev), faces, aux
+
+
+def save_obj(f, verts, faces, decimal_places=None):
+    """pytorch3d.io.save_obj, geometry only (deform_mesh_with_color.py / mesh_deformer.py end with it):
+    ``v x y z`` per vertex ("%f", or `decimal_places` digits) and 1-based ``f a b c`` per face, to a path or an
+    open text file."""
+    if verts.numel() and not (verts.dim() == 2 and verts.shape[1] == 3):
+        raise ValueError("Argument 'verts' should either be empty or of shape (num_verts, 3).")
+    if faces.numel() and not (faces.dim() == 2 and faces.shape[1] == 3):
+        raise ValueError("Argument 'faces' should either be empty or of shape (num_faces, 3).")
+    v = verts.detach().cpu().reshape(-1, 3).tolist()
+    fc = faces.detach().cpu().to(torch.int64).reshape(-1, 3)
+    if fc.numel() and (fc.min() < 0 or fc.max() >= len(v)):
+        raise ValueError("Faces have invalid indices")
+    fmt = "%f" if decimal_places is None else "%%.%df" % decimal_places
+    lines = ["v " + " ".join(fmt % x for x in row) for row in v]
+    lines += ["f %d %d %d" % (a + 1, b + 1, c + 1) for a, b, c in fc.tolist()]
+    text = "\n".join(lines) + ("\n" if lines else "")
+    if hasattr(f, "write"):
+        f.write(text)
+    else:
+        with open(os.fspath(f), "w") as fh:
+            fh.write(text)
 
 
 def load_objs_as_meshes(files, device=None, load_textures: bool = True, **_unused):

@@ -64,6 +64,171 @@ def vertex_adjacency(faces: torch.Tensor, V: int):
     return mesh_topology(faces, V)[1:]
 
 
+_PRIOR_CACHE: dict = {}
+
+
+class PriorTopology:
+    """What the shape-prior kernels (mr_mesh_priors_*) read of a batch of N meshes, in packed vertex ids and in
+    fixed sorted orders: ``edges`` (E,2) unique undirected edges, min first, sorted by min * V + max; ``nbr_ptr``
+    (V+1) / ``nbr`` (2E) each vertex's neighbours, ascending; ``pairs`` (P,4) = e0, e1, a, b for every unordered pair
+    of faces on edge (e0, e1) with opposite vertices a, b, sorted by (edge, face of a, face of b); ``pair_ptr`` (V+1)
+    / ``pair_idx`` (4P) each vertex's entries 4 * pair + role, ascending; the weights ``edge_w`` (E), ``pair_w`` (P)
+    and ``vert_w`` (V,2) = (Laplacian weight, edge weight of the vertex's mesh), each 1 / (elements of that kind in
+    the mesh * N). Index tensors are int32 on ``device``; the ``*_mesh_idx`` and count tensors int64."""
+
+    __slots__ = ("N", "V", "E", "P", "device", "edges", "edge_w", "nbr_ptr", "nbr", "vert_w", "pairs", "pair_w",
+                 "pair_ptr", "pair_idx", "edge_mesh_idx", "vert_mesh_idx", "num_edges_per_mesh", "__weakref__")
+
+
+def _csr_ptr(owner, n):
+    p = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(owner, minlength=n), out=p[1:])
+    return p
+
+
+def _build_prior_topology(faces_list, Vs, device) -> PriorTopology:
+    N = len(faces_list)
+    Vs = np.asarray(Vs, dtype=np.int64).reshape(N)
+    Vt = int(Vs.sum())
+    voff = np.cumsum(Vs) - Vs
+    fl = []
+    for m, f in enumerate(faces_list):
+        f = f.detach().to("cpu", torch.int64).numpy().reshape(-1, 3)
+        if f.size and (f.min() < 0 or f.max() >= Vs[m]):
+            raise ValueError("mesh priors: faces index vertices outside the mesh")
+        fl.append(f + voff[m])
+    fp = np.concatenate(fl, 0) if fl else np.zeros((0, 3), dtype=np.int64)
+    Fn = fp.shape[0]
+    if Vt >= 2 ** 31 // 3 or 3 * Fn >= 2 ** 29:
+        raise NotImplementedError("mesh priors: the packed batch is too large for 32-bit element ids")
+    # half-edges in upstream's order (v1 v2, v2 v0, v0 v1), each with the face's opposite vertex
+    ha = np.concatenate([fp[:, 1], fp[:, 2], fp[:, 0]])
+    hb = np.concatenate([fp[:, 2], fp[:, 0], fp[:, 1]])
+    opp = np.concatenate([fp[:, 0], fp[:, 1], fp[:, 2]])
+    key = np.minimum(ha, hb) * max(Vt, 1) + np.maximum(ha, hb)
+    ukey, inv = np.unique(key, return_inverse=True)
+    inv = inv.reshape(-1)
+    edges = np.stack([ukey // max(Vt, 1), ukey % max(Vt, 1)], 1)
+    E = edges.shape[0]
+    vmesh = np.repeat(np.arange(N, dtype=np.int64), Vs)
+    emesh = vmesh[edges[:, 0]]
+    e_per = np.bincount(emesh, minlength=N)
+    edge_w = 1.0 / (e_per[emesh] * float(N))
+    # vertex -> neighbours
+    src = np.concatenate([edges[:, 0], edges[:, 1]])
+    dst = np.concatenate([edges[:, 1], edges[:, 0]])
+    nbr = dst[np.lexsort((dst, src))]
+    nbr_ptr = _csr_ptr(src, Vt)
+    e_of_v = e_per[vmesh]
+    vert_w = np.stack([1.0 / (Vs[vmesh] * float(N)),
+                       np.where(e_of_v > 0, 1.0 / (np.maximum(e_of_v, 1) * float(N)), 0.0)], 1)
+    # face pairs on each edge: half-edges sorted by (edge, face, corner); an edge with k of them gives k (k - 1) / 2
+    hface = np.tile(np.arange(Fn, dtype=np.int64), 3)
+    hcorner = np.repeat(np.arange(3, dtype=np.int64), Fn)
+    opp_s = opp[np.lexsort((hcorner, hface, inv))]
+    cnt = np.bincount(inv, minlength=E)
+    start = np.cumsum(cnt) - cnt
+    pe, pi, pj = [], [], []
+    for i in range(int(cnt.max()) - 1 if E else 0):
+        for j in range(i + 1, int(cnt.max())):
+            sel = np.nonzero(cnt > j)[0]
+            pe.append(sel)
+            pi.append(np.full(sel.shape, i, dtype=np.int64))
+            pj.append(np.full(sel.shape, j, dtype=np.int64))
+    if pe:
+        pe, pi, pj = np.concatenate(pe), np.concatenate(pi), np.concatenate(pj)
+        o = np.lexsort((pj, pi, pe))
+        pe, pi, pj = pe[o], pi[o], pj[o]
+        pairs = np.stack([edges[pe, 0], edges[pe, 1], opp_s[start[pe] + pi], opp_s[start[pe] + pj]], 1)
+    else:
+        pairs = np.zeros((0, 4), dtype=np.int64)
+    P = pairs.shape[0]
+    pmesh = vmesh[pairs[:, 0]]
+    pair_w = 1.0 / (np.bincount(pmesh, minlength=N)[pmesh] * float(N))
+    # vertex -> (pair, role), ascending
+    pvert = pairs.reshape(-1)
+    pair_idx = np.argsort(pvert, kind="stable")
+    pair_ptr = _csr_ptr(pvert, Vt)
+
+    t = PriorTopology()
+    t.N, t.V, t.E, t.P, t.device = N, Vt, E, P, device
+
+    def dev(a, dtype):
+        return torch.from_numpy(np.ascontiguousarray(a.astype(dtype))).to(device)
+
+    t.edges, t.edge_w = dev(edges, np.int32), dev(edge_w, np.float32)
+    t.nbr_ptr, t.nbr, t.vert_w = dev(nbr_ptr, np.int32), dev(nbr, np.int32), dev(vert_w, np.float32)
+    t.pairs, t.pair_w = dev(pairs, np.int32), dev(pair_w, np.float32)
+    t.pair_ptr, t.pair_idx = dev(pair_ptr, np.int32), dev(pair_idx, np.int32)
+    t.edge_mesh_idx, t.vert_mesh_idx = dev(emesh, np.int64), dev(vmesh, np.int64)
+    t.num_edges_per_mesh = dev(e_per, np.int64)
+    return t
+
+
+def mesh_prior_topology(faces_list, Vs) -> PriorTopology:
+    """The PriorTopology of the meshes (faces_list[m] (F_m,3) over Vs[m] vertices), built on the host once per
+    faces tensors and cached like mesh_topology: on the identity and version of each tensor, so a steady
+    deformation loop (whose Meshes.offset_verts result keeps the source's faces tensors) or a captured HIP graph
+    does no host work and no sync here."""
+    faces_list = list(faces_list)
+    Vs = tuple(int(v) for v in Vs)
+    key = tuple(id(f) for f in faces_list) + Vs
+    hit = _PRIOR_CACHE.get(key)
+    if hit is not None and all(r() is f and ver == f._version for r, ver, f in zip(hit[0], hit[1], faces_list)):
+        return hit[2]
+    device = faces_list[0].device if faces_list else torch.device("cpu")
+    topo = _build_prior_topology(faces_list, Vs, device)
+    if len(_PRIOR_CACHE) > 64:
+        _PRIOR_CACHE.clear()
+    _PRIOR_CACHE[key] = ([weakref.ref(f) for f in faces_list], [f._version for f in faces_list], topo)
+    return topo
+
+
+class MeshShapePriors(torch.autograd.Function):
+    """(edge, Laplacian, normal-consistency) losses of packed vertices (V,3) over a PriorTopology: two launches
+    forward (mr_mesh_priors_forward: one pass over edges, vertices and pairs, then the fixed-order reduction) and
+    one backward (mr_mesh_priors_backward: a per-vertex gather scaled by the three upstream scalars on the device).
+    ``terms`` (MR_PRIOR_* mask) picks the terms computed; the others come out 0 and carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, verts, topo, target_length, terms):
+        _require_cuda(verts)
+        L = _lib.load()
+        v = verts.detach().float().contiguous()
+        if tuple(v.shape) != (topo.V, 3):
+            raise ValueError(f"mesh priors: verts must be ({topo.V}, 3), got {tuple(v.shape)}")
+        if topo.device != v.device:
+            raise RuntimeError("mesh priors: faces and vertices live on different devices")
+        want = bool(ctx.needs_input_grad[0])
+        out = torch.empty(3, device=v.device)
+        wsb = _ws_size(L.mr_mesh_priors_workspace, topo.V, topo.E, topo.P)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=v.device)
+        check(L.mr_mesh_priors_forward(ptr(v), topo.V, ptr(topo.edges), ptr(topo.edge_w), topo.E, ptr(topo.nbr_ptr),
+                                       ptr(topo.nbr), ptr(topo.vert_w), ptr(topo.pairs), ptr(topo.pair_w), topo.P,
+                                       float(target_length), int(terms), int(want), ptr(out), ptr(ws), wsb,
+                                       _lib.stream_handle(v.device)))
+        ctx.set_materialize_grads(False)
+        if want:
+            ctx.save_for_backward(v, ws)
+            ctx.args = (topo, float(target_length), int(terms), verts.dtype)
+        return out[0], out[1], out[2]
+
+    @staticmethod
+    def backward(ctx, g_edge, g_lap, g_norm):
+        if g_edge is None and g_lap is None and g_norm is None:
+            return None, None, None, None
+        v, ws = ctx.saved_tensors
+        topo, target_length, terms, dtype = ctx.args
+        gs = [None if g is None else g.detach().float().contiguous() for g in (g_edge, g_lap, g_norm)]
+        _require_cuda(*gs)
+        gv = torch.empty_like(v)
+        check(_lib.load().mr_mesh_priors_backward(ptr(v), topo.V, ptr(topo.nbr_ptr), ptr(topo.nbr), ptr(topo.vert_w),
+                                                  ptr(topo.pair_ptr), ptr(topo.pair_idx), topo.E, topo.P, target_length,
+                                                  terms, ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(ws), ptr(gv),
+                                                  _lib.stream_handle(v.device)))
+        return gv.to(dtype), None, None, None
+
+
 def raster_settings_struct(H, W, K=1, blur=0.0, persp=True, clip=False, cull=False, max_faces_per_bin=None,
                            z_clip=None):
     """mr_raster_settings_t; z_clip = z_clip_value of the near-plane clip (None: no clipping)."""

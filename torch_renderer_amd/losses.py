@@ -1,4 +1,13 @@
-"""Fused pose-optimiser loss.
+"""Fused losses: the pose optimiser's loss and the mesh shape priors of the deformation loops.
+
+Mesh shape priors (``pytorch3d.loss.mesh_edge_loss`` / ``mesh_laplacian_smoothing`` / ``mesh_normal_consistency``,
+called together by update_mesh_shape_prior_losses at deform_mesh_with_color.py:248-256 and mesh_deformer.py:
+314-320): ``mesh_shape_priors`` returns all three from one autograd node — one HIP pass over the edges,
+vertices and face pairs plus a fixed-order reduction forward, one gathering launch backward
+(kernels.MeshShapePriors, csrc/mr_priors.hip) — instead of ~40 torch index / elementwise launches each way. The
+three upstream-named functions run the same node with only their own term switched on. Deterministic.
+
+Fused pose-optimiser loss.
 
 ``pose_loss`` is camera_pose_optimizer.py:257-276 ``Model.calc_loss`` in three HIP launches forward
 (mask count, one pass that sums the loss AND writes its gradients for dL/dtotal = 1, final reduction)
@@ -23,7 +32,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .kernels import _require_cuda
+from .kernels import MeshShapePriors, _require_cuda, mesh_prior_topology
 
 
 def _rgba_base(t: torch.Tensor, channels):
@@ -57,3 +66,51 @@ def pose_loss(depth, silhouette, color, mask, depth_ref, rgb_ref, delta: float =
     if return_terms:
         return total, (terms[0], terms[1], terms[2])
     return total
+
+
+def _mesh_priors(meshes, target_length: float, terms: int):
+    """(edge, laplacian, normal) of `meshes`, computing the terms in the MR_PRIOR_* mask `terms`."""
+    if meshes.isempty():  # upstream: a zero that requires grad
+        dev = meshes.device if len(meshes) else torch.device("cpu")
+        return tuple(torch.zeros(1, dtype=torch.float32, device=dev, requires_grad=True) for _ in range(3))
+    if meshes.is_shared():
+        # one mesh, or Meshes.extend(N): N equal meshes weighted 1/N each are the single mesh, and its
+        # vertices take the gradient once
+        verts, faces = meshes.shared_verts(), [meshes.shared_faces()]
+        sizes = [verts.shape[0]]
+    else:
+        vl, faces = meshes.verts_list(), meshes.faces_list()
+        sizes = [v.shape[0] for v in vl]
+        verts = torch.cat(vl, 0)
+    _require_cuda(verts, *faces)
+    return MeshShapePriors.apply(verts, mesh_prior_topology(faces, sizes), float(target_length), terms)
+
+
+def mesh_shape_priors(meshes, target_length: float = 0.0):
+    """(mesh_edge_loss(meshes, target_length), mesh_laplacian_smoothing(meshes, "uniform"),
+    mesh_normal_consistency(meshes)) from ONE autograd node and one forward pass: what a deformation loop's
+    update_mesh_shape_prior_losses should call. Each is a 0-dim float32 tensor on the meshes' device,
+    differentiable w.r.t. the vertex tensors of `meshes`."""
+    return _mesh_priors(meshes, target_length, _lib.MR_PRIOR_ALL)
+
+
+def mesh_edge_loss(meshes, target_length: float = 0.0):
+    """pytorch3d.loss.mesh_edge_loss: per mesh the mean over its unique edges of (|v0 - v1| - target_length)^2,
+    averaged over the meshes."""
+    return _mesh_priors(meshes, target_length, _lib.MR_PRIOR_EDGE)[0]
+
+
+def mesh_laplacian_smoothing(meshes, method: str = "uniform"):
+    """pytorch3d.loss.mesh_laplacian_smoothing(method="uniform"): per mesh the mean over its vertices of
+    |mean of the neighbours - v|, averaged over the meshes. The cotangent weightings are not built."""
+    if method in ("cot", "cotcurv"):
+        raise NotImplementedError(f"mesh_laplacian_smoothing: method {method!r} is not built (only 'uniform')")
+    if method != "uniform":
+        raise ValueError("Method should be one of {uniform, cot, cotcurv}")
+    return _mesh_priors(meshes, 0.0, _lib.MR_PRIOR_LAPLACIAN)[1]
+
+
+def mesh_normal_consistency(meshes):
+    """pytorch3d.loss.mesh_normal_consistency: per mesh the mean over the pairs of faces sharing an edge of
+    1 - cos(angle between their normals), averaged over the meshes (0 for a mesh without such pairs)."""
+    return _mesh_priors(meshes, 0.0, _lib.MR_PRIOR_NORMAL)[2]

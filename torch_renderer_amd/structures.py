@@ -233,6 +233,25 @@ class Meshes:
         counts = self.num_faces_per_mesh()
         return torch.cumsum(counts, 0) - counts
 
+    def _prior_topology(self):
+        from .kernels import mesh_prior_topology
+
+        return mesh_prior_topology(self.faces_list(), [v.shape[0] for v in self.verts_list()])
+
+    def edges_packed(self):
+        """(E,2) int64 unique undirected edges over packed vertex ids, min first, sorted by min * V + max
+        (upstream order). Built on the host once per faces tensors (kernels.mesh_prior_topology)."""
+        return self._prior_topology().edges.to(torch.int64)
+
+    def num_edges_per_mesh(self):
+        return self._prior_topology().num_edges_per_mesh
+
+    def edges_packed_to_mesh_idx(self):
+        return self._prior_topology().edge_mesh_idx
+
+    def verts_packed_to_mesh_idx(self):
+        return self._prior_topology().vert_mesh_idx
+
     def verts_normals_packed(self):
         from .kernels import vertex_normals
 
