@@ -100,6 +100,48 @@ def test_world_rasterizer_validation_and_workspace(lib):
     assert ctypes.sizeof(_lib.MrPoses) == ctypes.sizeof(_lib.MrOpencvPoses) == 48
 
 
+@pytest.mark.parametrize("entry", ["mr_render_forward", "mr_render_forward_poses", "mr_render_forward_opencv",
+                                   "mr_render_reshade"])
+def test_fused_render_validation_is_shared(lib, entry):
+    """The fused render's forwards and its reshade reject the same bad arguments with the same status and
+    message, before any launch or memset (no GPU here): a one-face mesh over host memory that is never read,
+    ambient light, a 64x64 K = 1 raster, and one thing broken at a time."""
+    buf = ctypes.create_string_buffer(256)
+    p = ctypes.addressof(buf)  # non-NULL, never dereferenced
+
+    def call(K=1, flags=_lib.MR_OUT_DEPTH | _lib.MR_OUT_SIL | _lib.MR_OUT_RGB, N=1, channels=3, depth=p,
+             ws_bytes=1 << 40):
+        mesh = _lib.MrMesh()
+        mesh.verts = mesh.faces = mesh.vadj_ptr = mesh.vadj = p
+        mesh.V = mesh.F = 1
+        sp = _lib.MrShadeParams()
+        sp.light_kind, sp.out_flags, sp.rgb_channels = 1, flags, channels
+        sp.sigma_rgb = sp.gamma = sp.sigma_sil = 1e-4
+        sp.znear, sp.zfar = 1.0, 100.0
+        s = _lib.MrRasterSettings()
+        s.H, s.W, s.faces_per_pixel, s.blur_radius = 64, 64, K, 0.0
+        tail = (N, None, 0, ctypes.byref(s), ctypes.byref(sp), depth, p, p, None, p, ws_bytes, None)
+        if entry == "mr_render_forward_poses":
+            rc = lib.mr_render_forward_poses(ctypes.byref(mesh), ctypes.byref(_lib.MrPoses(p, 0, p, 0, p, 0)), p, *tail)
+        elif entry == "mr_render_forward_opencv":
+            rc = lib.mr_render_forward_opencv(ctypes.byref(mesh), ctypes.byref(_lib.MrOpencvPoses(p, 0, p, 0, p, 0)), p,
+                                              *tail)
+        else:
+            rc = getattr(lib, entry)(ctypes.byref(mesh), p, *tail)
+        return rc, lib.mr_last_error()
+
+    rc, msg = call(K=2)
+    assert rc == 3 and b"K = 1" in msg
+    rc, msg = call(flags=_lib.MR_OUT_RGB | _lib.MR_OUT_HARD)
+    assert rc == 3 and b"hard_rgb_blend" in msg
+    assert call(N=0)[0] == 1
+    assert call(channels=5)[0] == 1
+    rc, msg = call(depth=None)
+    assert rc == 1 and b"depth" in msg
+    rc, msg = call(ws_bytes=0)
+    assert rc == 4 and b"workspace too small" in msg  # MR_EWORKSPACE
+
+
 def header_enum(names_prefix=("MR_OUT_", "MR_GRAD_", "MR_FRAG_", "MR_SREC_")):
     src = open(os.path.join(ROOT, "include", "mi355r.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)

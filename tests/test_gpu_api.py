@@ -139,14 +139,25 @@ def test_mesh_rasterizer_fragments_bitexact(distinct):
         _close(f"MeshRasterizer fragments (distinct={distinct}) {nm}", a.grad, b.grad)
 
 
-@pytest.mark.parametrize("shader,W", [("phong", 64), ("silhouette", 64), ("silhouette", 66)])
+@pytest.mark.parametrize("shader,W", [("phong", 64), ("silhouette", 64), ("silhouette", 66), ("phong", 2052)])
 def test_mesh_renderer_matches_oracle(shader, W):
     """Cameras built with R, T (renderer.py:65-69): specular uses the real camera centre. The
     silhouette's RGBA (1, 1, 1, alpha) comes straight from the kernels (W = 66: the per-pixel
-    background stores instead of the 4-pixel vector ones)."""
-    H, N = 64, 2
-    verts, faces, d = mesh_arrays("teapot")
-    R, T, intr, (R_cv, t_cv, K) = canonical_views(verts, N, H, W)
+    background stores instead of the 4-pixel vector ones). W = 2052: one view of the sphere, 16 rows high; its
+    257 x 2 tile grid is wider than the per-view binning takes, so PyTorch3D-convention poses reach the
+    count -> scan path (mr_render_forward_poses: the view records from k_views_from_cv).
+
+    The W = 2052 camera has a focal length of 32 px, so the whole sphere (radius ~7.5 px) lies inside the 16 rows
+    and its NDC coordinates stay within ~1, as in the other cases (NDC units are min(H, W) / 2 = 8 px here). With
+    the 60 degree field of view of the other cases f = 1777 px: the view is a 16-row strip of a ~400 px sphere at
+    NDC |x| up to ~50, where float32 coordinates resolve the blend's sigma = 1e-4 so coarsely that the float32
+    oracle is itself 377 x this test's bar from its float64 shadow on grad verts (199 entries over); no float32
+    renderer can be held to the bar against it. At f = 32 px the oracle is 1.2 x the bar from its shadow (2
+    entries; W = 64 teapot: 3.3 x, 5 entries), the sphere covers 172 pixels and 576 vertices get a gradient."""
+    H, N, asset = (16, 1, "sphere") if W == 2052 else (64, 2, "teapot")
+    verts, faces, d = mesh_arrays(asset)
+    fov = math.degrees(2.0 * math.atan((W / 2.0) / 32.0)) if W == 2052 else 60.0
+    R, T, intr, (R_cv, t_cv, K) = canonical_views(verts, N, H, W, fov_deg=fov)
     g = torch.Generator().manual_seed(11)
     vcol = torch.rand(verts.shape, generator=g)
     cams = PerspectiveCameras(focal_length=((K[0, 0].item(), K[1, 1].item()),),

@@ -696,8 +696,9 @@ struct NormalsArgs {
   float4* zero4b;  // ... and their float remainder rows (nzero4b 16-B words)
   int64_t nzero4b;
 };
-// OpenCV poses converted on the fly (mr_render_forward_opencv): element k of view n's record,
-// as k_views_from_opencv writes it (torch_renderer.py:73-80; bitwise the torch conversion).
+// Pose arrays turned into view records on the fly (mr_render_forward_opencv / _poses, k_views_from_cv):
+// element k of view n's record; the library's one OpenCV conversion (torch_renderer.py:73-80; bitwise the
+// torch conversion).
 struct CvPoses {
   const float* R;  // NULL: the view records are given
   int64_t sR;

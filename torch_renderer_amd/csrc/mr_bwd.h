@@ -912,3 +912,19 @@ __global__ void __launch_bounds__(256) k_rt_reduce(const float* __restrict__ par
                                                    float* __restrict__ gtcv) {
   rt_reduce_view(part, vslot, N, bands, out, gRcv, gtcv, blockIdx.x);
 }
+
+#ifndef MR_BWD_GRID_MUL
+#define MR_BWD_GRID_MUL 1
+#endif
+// One k_bwd_fused instantiation over the NT = N * T tile slots of a forward: its resident grid (sized on the first
+// call), capped to enough waves for every tile, a multiple of 8 (XCD-partitioned slot ranges).
+template <int ACC, bool CLIP, bool GEO = false, int SPEC = 0>
+static int launch_bwd_fused(const RenderBwdParams& P, int64_t NT, hipStream_t st) {
+  static int grid = 0;
+  if (!grid) grid = resident_grid(k_bwd_fused<ACC, CLIP, GEO, SPEC>, 256, GEO ? 4 : ACC == 27 ? 2 : 3);
+  const int gr = grid * MR_BWD_GRID_MUL;
+  const int c = (int)(NT / 4 + 1 < gr ? NT / 4 + 1 : gr);
+  MR_TIMED(KID_BWD_FUSED, st, (k_bwd_fused<ACC, CLIP, GEO, SPEC><<<(c + 7) / 8 * 8, 256, 0, st>>>(P)));
+  MR_CHECK_LAUNCH("k_bwd_fused");
+  return MR_OK;
+}

@@ -2,11 +2,12 @@
 // below are included in order; this file holds the extern "C" entry points of include/mi355r.h).
 //
 // Pipeline for a batch of N views (all launches async on one stream, no host sync):
-//   1. binning (mr_bin.h): k_bin_rect_world projects every (view, face) — OpenCV pose conversion and
-//      near-plane clipping inline — and writes its 64-B FaceRec and 8x8-tile rectangle; one 1024-thread
-//      workgroup per view (k_bin_view) histograms, scans and fills the view's tile lists in LDS and
-//      emits slots (non-empty tiles) and work UNITS of <= 64 (tile, face) entries. Large grids take
-//      the count -> scan -> fill path.
+//   1. binning (mr_bin.h): k_bin_rect_world projects every (view, face) — pose conversion (cv_view_elem,
+//      either convention) and near-plane clipping inline — and writes its 64-B FaceRec and 8x8-tile
+//      rectangle; 1024-thread workgroups, one per (view, band of tile rows) (k_bin_view), histogram, scan
+//      and fill the tile lists in LDS and emit slots (non-empty tiles) and work UNITS of <= 64 (tile, face)
+//      entries; the workgroup slots they leave free pack the ShadeRecs and stream background. Large grids
+//      take the count -> scan -> fill path (view records first: k_views_from_cv).
 //   2. K = 1 raster (mr_tile_raster.h): k_tile_raster, a persistent grid of independent waves
 //      (XCD-partitioned units, 3-deep unit/list/record prefetch); each lane turns one face into an 8x8
 //      coverage mask, the wave evaluates the (face, pixel) pairs 64 at a time exactly and keeps the
@@ -21,6 +22,13 @@
 //   4. vertex kernels (mr_vertex.h) gather per-face rows through a CSR vertex adjacency
 //      (deterministic order) and chain the vertex-normal backward.
 //   5. K-deep shading over stored fragments (mr_frag_shade.h) and the fused pose loss (mr_loss.h).
+//
+// Host side: an entry point checks its arguments, fills the kernels' parameter structs (make_setup, make_fwd,
+// make_shade, make_raster_bwd; cv_poses for pose arrays; render_call for what the fused forward and its reshade
+// share) and calls one launcher per kernel family, which owns that family's template ladder, grid and timing
+// id: launch_bin_rect_world, launch_bin_view, launch_scan and launch_views_from_cv here,
+// launch_raster_and_shade / launch_fill_and_shade (mr_tile_raster.h), launch_raster_k (mr_kdeep.h),
+// launch_bwd_fused (mr_bwd.h) and launch_vertex_grads (mr_vertex.h) beside their kernels.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -77,7 +85,7 @@ size_t mr_rasterize_meshes_workspace(int64_t num_meshes, int64_t total_faces, in
                                      int32_t max_faces_per_bin) {
   const int64_t Ftot = total_faces > 0 ? total_faces : 1;
   BinGeom g = bin_geom(H, W, num_meshes, Ftot, max_faces_per_bin);
-  return carve_raster_ws(nullptr, num_meshes, Ftot, H, W, g).bytes;
+  return carve_raster_ws(nullptr, num_meshes, Ftot, g).bytes;
 }
 
 static SetupParams make_setup(const mr_raster_settings_t* s, const BinGeom& g, const RasterWS& w) {
@@ -172,8 +180,7 @@ static int64_t bin_bg_wgs(int64_t nbin, int64_t sb, bool banded) {
 #ifndef MR_SREC_FPW
 #define MR_SREC_FPW 1024
 #endif
-static int64_t srec_wgs(int64_t F, int64_t nbin, int* fpw_out = nullptr) {
-  (void)nbin;
+static int64_t srec_wgs(int64_t F, int* fpw_out = nullptr) {
   if (F <= 0) return 0;
   if (fpw_out) *fpw_out = MR_SREC_FPW;
   return ceil_div(F, MR_SREC_FPW);
@@ -207,7 +214,7 @@ static int launch_bin_view(const SetupParams& SP, const RasterWS& w, const BinGe
   const int B = bin_bands(N, g);
   V.bands = B;
   const int64_t nbin = N * B;
-  if (S) sb = srec_wgs(F, nbin, &V.srec_fpw);
+  if (S) sb = srec_wgs(F, &V.srec_fpw);
   V.nsrec_wg = (int)sb;
   V.list_cap = g.list_cap; V.NF = SP.NF;
   V.rects = w.rects; V.first = first; V.view_count = view_count; V.F = F;
@@ -241,6 +248,47 @@ static int launch_bin_view(const SetupParams& SP, const RasterWS& w, const BinGe
 }
 }  // extern "C++"
 
+// k_bin_rect_world<clip_z> over `grid`: row 0 the clears (and NA's normals), rows 1 .. N the views' records,
+// rows past them B's background chunks.
+static int launch_bin_rect_world(const SetupParams& SP, dim3 grid, const float* verts, const int32_t* faces, int64_t F,
+                                 const mr_view_t* views, const NormalsArgs& NA, int* ctr, const CvPoses& C,
+                                 const FragBg& B, hipStream_t st) {
+  const ViewRec* vr = (const ViewRec*)views;
+  if (SP.clipz) MR_TIMED(KID_BIN_RECT, st, (k_bin_rect_world<true><<<grid, 256, 0, st>>>(SP, verts, faces, F, vr, NA, ctr, C, B)));
+  else MR_TIMED(KID_BIN_RECT, st, (k_bin_rect_world<false><<<grid, 256, 0, st>>>(SP, verts, faces, F, vr, NA, ctr, C, B)));
+  MR_CHECK_LAUNCH("k_bin_rect_world");
+  return MR_OK;
+}
+
+// The pose arrays of mr_poses_t / mr_opencv_poses_t (one layout, two conventions) as the kernels' CvPoses,
+// `out` the (N,16) view records they write.
+static int cv_poses(CvPoses* C, const float* R, int64_t sR, const float* t, int64_t sT, const float* intr, int64_t sI,
+                    mr_view_t* out, int opencv) {
+  if (!R || !t || !intr || !out) return set_err(MR_EINVAL, "NULL pose argument");
+  if (sR < 0 || sT < 0 || sI < 0) return set_err(MR_EINVAL, "negative stride");
+  C->R = R; C->sR = sR; C->t = t; C->sT = sT; C->intr = intr; C->sI = sI;
+  C->out = (float*)out; C->opencv = opencv;
+  return MR_OK;
+}
+
+// View records from the pose arrays (either convention, cv_view_elem): mr_views_from_opencv and the count ->
+// scan paths. With `first`: also the shared-mesh face ranges (first[n] = n F, count[n] = F) the count -> scan
+// fallback of mr_rasterize_meshes_world reads.
+__global__ void __launch_bounds__(256) k_views_from_cv(CvPoses C, int64_t N, int64_t F, int64_t* __restrict__ first,
+                                                       int64_t* __restrict__ count) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < N * 16) C.out[i] = cv_view_elem(C, i >> 4, (int)(i & 15));
+  if (first && i < N) {
+    first[i] = i * F;
+    count[i] = F;
+  }
+}
+static int launch_views_from_cv(const CvPoses& C, int64_t N, hipStream_t st, int64_t F = 0, int64_t* first = nullptr) {
+  k_views_from_cv<<<ceil_div(N * 16, 256), 256, 0, st>>>(C, N, F, first, first ? first + N : nullptr);
+  MR_CHECK_LAUNCH("k_views_from_cv");
+  return MR_OK;
+}
+
 int32_t mr_per_view_binning(int64_t N, int64_t total_faces, int32_t H, int32_t W) {
   if (N <= 0 || H <= 0 || W <= 0) return 0;
   const int64_t Ft = total_faces > 0 ? total_faces : 1;
@@ -252,7 +300,7 @@ int64_t mr_binning_background_pixels(int64_t N, int64_t F, int32_t H, int32_t W,
   BinGeom g = bin_geom(H, W, N, N * (F > 0 ? F : 1), 0);
   if (!view_binning(g, N, N * (F > 0 ? F : 1))) return 0;
   const int64_t nbin = N * bin_bands(N, g);
-  const int64_t sb = mode == 1 ? srec_wgs(F, nbin) : 0;
+  const int64_t sb = mode == 1 ? srec_wgs(F) : 0;
   const int64_t px = bg_chunks(N, nbin, sb, H, W, mode) * ((W & 3) == 0 ? 256 : 64);
   return std::min<int64_t>(px, N * (int64_t)H * W);
 }
@@ -270,7 +318,7 @@ int32_t mr_rasterize_meshes(const float* face_verts, const int64_t* first, const
   hipStream_t st = (hipStream_t)stream;
   const int64_t Fb = Ftot > 0 ? Ftot : 1;
   BinGeom g = bin_geom(s->H, s->W, N, Fb, s->max_faces_per_bin);
-  RasterWS w = carve_raster_ws(ws, N, Fb, s->H, s->W, g);
+  RasterWS w = carve_raster_ws(ws, N, Fb, g);
   if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "workspace too small: %zu < %zu", ws_bytes, w.bytes);
   const bool vpath = view_binning(g, N, Fb);
   // per-view path: k_bin_rect_fv clears the counters
@@ -313,25 +361,6 @@ int32_t mr_rasterize_meshes(const float* face_verts, const int64_t* first, const
   return launch_raster_and_shade<0, 3>(P, g, N, st, s->clip_z != 0);
 }
 
-// View records from PyTorch3D poses, and the shared-mesh face ranges (first[n] = n F, count F)
-// the count -> scan fallback of mr_rasterize_meshes_world reads.
-__global__ void __launch_bounds__(256) k_views_from_poses(CvPoses C, int64_t N, int64_t F, int64_t* __restrict__ first,
-                                                          int64_t* __restrict__ count) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N * 16) C.out[i] = cv_view_elem(C, i >> 4, (int)(i & 15));
-  if (i < N) {
-    first[i] = i * F;
-    count[i] = F;
-  }
-}
-
-// View records from the pose arrays (either convention, cv_view_elem), the count -> scan path of the
-// fused render.
-__global__ void __launch_bounds__(256) k_views_from_cv(CvPoses C, int64_t N) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N * 16) C.out[i] = cv_view_elem(C, i >> 4, (int)(i & 15));
-}
-
 size_t mr_rasterize_meshes_world_workspace(int64_t N, int64_t F, int32_t H, int32_t W, int32_t max_faces_per_bin) {
   return align_up(mr_rasterize_meshes_workspace(N, N * F, H, W, max_faces_per_bin), 256) +
          align_up(sizeof(int64_t) * 2 * (size_t)(N > 0 ? N : 1), 256);
@@ -351,27 +380,26 @@ int32_t mr_rasterize_meshes_world(const float* verts, int64_t V, const int32_t* 
   if (N <= 0 || N > 65535) return set_err(MR_EINVAL, "N must be in [1, 65535] (got %lld)", (long long)N);
   if (F < 0 || V < 0 || N * F >= (1ll << 30)) return set_err(MR_EINVAL, "F / V out of range");
   if ((int64_t)N * s->H * s->W >= (1ll << 31)) return set_err(MR_EUNSUPPORTED, "N*H*W >= 2^31");
-  if (!poses || !poses->R || !poses->T || !poses->intr || !views_out || !p2f || !zbuf || !bary || !dists ||
-      (F > 0 && (!verts || !faces || !face_verts)))
+  if (!poses) return set_err(MR_EINVAL, "NULL pose argument");
+  CvPoses C;
+  if ((rc = cv_poses(&C, poses->R, poses->R_stride, poses->T, poses->T_stride, poses->intr, poses->intr_stride,
+                     views_out, 0)))
+    return rc;
+  if (!p2f || !zbuf || !bary || !dists || (F > 0 && (!verts || !faces || !face_verts)))
     return set_err(MR_EINVAL, "NULL argument");
-  if (poses->R_stride < 0 || poses->T_stride < 0 || poses->intr_stride < 0) return set_err(MR_EINVAL, "negative stride");
   const size_t need = mr_rasterize_meshes_world_workspace(N, F, s->H, s->W, s->max_faces_per_bin);
   if (ws_bytes < need) return set_err(MR_EWORKSPACE, "workspace too small: %zu < %zu", ws_bytes, need);
   hipStream_t st = (hipStream_t)stream;
-  CvPoses C;
-  C.R = poses->R; C.sR = poses->R_stride; C.t = poses->T; C.sT = poses->T_stride;
-  C.intr = poses->intr; C.sI = poses->intr_stride; C.out = (float*)views_out; C.opencv = 0;
   const int64_t Fb = N * F > 0 ? N * F : 1;
   BinGeom g = bin_geom(s->H, s->W, N, Fb, s->max_faces_per_bin);
   if (F == 0 || !view_binning(g, N, Fb)) {
     const size_t rws = align_up(mr_rasterize_meshes_workspace(N, N * F, s->H, s->W, s->max_faces_per_bin), 256);
     int64_t* first = (int64_t*)((char*)ws + rws);
-    k_views_from_poses<<<ceil_div(N * 16, 256), 256, 0, st>>>(C, N, F, first, first + N);
-    MR_CHECK_LAUNCH("k_views_from_poses");
+    if ((rc = launch_views_from_cv(C, N, st, F, first))) return rc;
     if ((rc = mr_project_faces(verts, V, faces, F, views_out, N, face_verts, stream))) return rc;
     return mr_rasterize_meshes(face_verts, first, first + N, N, N * F, s, p2f, zbuf, bary, dists, ws, rws, stream);
   }
-  RasterWS w = carve_raster_ws(ws, N, Fb, s->H, s->W, g);
+  RasterWS w = carve_raster_ws(ws, N, Fb, g);
   SetupParams SP = make_setup(s, g, w);
   SP.NF = Fb;
   SP.fv_out = face_verts;
@@ -394,9 +422,7 @@ int32_t mr_rasterize_meshes_world(const float* verts, int64_t V, const int32_t* 
       rgrid.y += MR_BG_RECT_ROWS;
     }
   }
-  if (SP.clipz) MR_TIMED(KID_BIN_RECT, st, (k_bin_rect_world<true><<<rgrid, 256, 0, st>>>(SP, verts, faces, F, (const ViewRec*)views_out, NA, w.ctr, C, FB)));
-  else MR_TIMED(KID_BIN_RECT, st, (k_bin_rect_world<false><<<rgrid, 256, 0, st>>>(SP, verts, faces, F, (const ViewRec*)views_out, NA, w.ctr, C, FB)));
-  MR_CHECK_LAUNCH("k_bin_rect_world");
+  if ((rc = launch_bin_rect_world(SP, rgrid, verts, faces, F, views_out, NA, w.ctr, C, FB, st))) return rc;
   if (s->faces_per_pixel > 1) {
     if ((rc = launch_bin_view(SP, w, g, N, nullptr, nullptr, F, true, st))) return rc;
     return launch_raster_k(P, g, N, st);
@@ -427,7 +453,7 @@ static SilWS carve_sil(void* base, size_t raster_bytes, int64_t NT, int K) {
 size_t mr_soft_silhouette_workspace(int64_t N, int64_t F, int32_t H, int32_t W, int32_t K, int32_t max_faces_per_bin) {
   const int64_t Fb = N * F > 0 ? N * F : 1;
   BinGeom g = bin_geom(H, W, N, Fb, max_faces_per_bin);
-  const size_t rb = carve_raster_ws(nullptr, N, Fb, H, W, g).bytes;
+  const size_t rb = carve_raster_ws(nullptr, N, Fb, g).bytes;
   return carve_sil(nullptr, rb, N * (int64_t)g.T, K > 0 ? K : 1).bytes;
 }
 
@@ -443,20 +469,20 @@ int32_t mr_soft_silhouette_forward(const float* verts, int64_t V, const int32_t*
   if (F <= 0 || V <= 0 || N * F >= (1ll << 30)) return set_err(MR_EINVAL, "F / V out of range");
   if ((int64_t)N * s->H * s->W >= (1ll << 31)) return set_err(MR_EUNSUPPORTED, "N*H*W >= 2^31");
   if (!(sigma > 0.0f)) return set_err(MR_EINVAL, "sigma must be > 0");
-  if (!poses || !poses->R || !poses->T || !poses->intr || !views_out || !verts || !faces || !face_verts || !rgba)
-    return set_err(MR_EINVAL, "NULL argument");
-  if (poses->R_stride < 0 || poses->T_stride < 0 || poses->intr_stride < 0) return set_err(MR_EINVAL, "negative stride");
+  if (!poses) return set_err(MR_EINVAL, "NULL pose argument");
+  CvPoses C;
+  if ((rc = cv_poses(&C, poses->R, poses->R_stride, poses->T, poses->T_stride, poses->intr, poses->intr_stride,
+                     views_out, 0)))
+    return rc;
+  if (!verts || !faces || !face_verts || !rgba) return set_err(MR_EINVAL, "NULL argument");
   const int64_t Fb = N * F;
   BinGeom g = bin_geom(s->H, s->W, N, Fb, s->max_faces_per_bin);
   if (!view_binning(g, N, Fb)) return set_err(MR_EUNSUPPORTED, "fused soft silhouette: per-view binning sizes only");
   if ((int64_t)N * g.T * 64 * K >= (1ll << 31)) return set_err(MR_EUNSUPPORTED, "N*T*64*K >= 2^31");
-  RasterWS w = carve_raster_ws(ws, N, Fb, s->H, s->W, g);
+  RasterWS w = carve_raster_ws(ws, N, Fb, g);
   SilWS sw = carve_sil(ws, w.bytes, N * (int64_t)g.T, K);
   if (ws_bytes < sw.bytes) return set_err(MR_EWORKSPACE, "workspace too small: %zu < %zu", ws_bytes, sw.bytes);
   hipStream_t st = (hipStream_t)stream;
-  CvPoses C;
-  C.R = poses->R; C.sR = poses->R_stride; C.t = poses->T; C.sT = poses->T_stride;
-  C.intr = poses->intr; C.sI = poses->intr_stride; C.out = (float*)views_out; C.opencv = 0;
   SetupParams SP = make_setup(s, g, w);
   SP.NF = Fb;
   SP.fv_out = face_verts;
@@ -467,13 +493,23 @@ int32_t mr_soft_silhouette_forward(const float* verts, int64_t V, const int32_t*
   NormalsArgs NA;
   memset(&NA, 0, sizeof(NA));
   dim3 rgrid((unsigned)ceil_div(F, 256), (unsigned)N + 1);  // row 0: counter clear
-  if (SP.clipz) MR_TIMED(KID_BIN_RECT, st, (k_bin_rect_world<true><<<rgrid, 256, 0, st>>>(SP, verts, faces, F, (const ViewRec*)views_out, NA, w.ctr, C, FragBg{})));
-  else MR_TIMED(KID_BIN_RECT, st, (k_bin_rect_world<false><<<rgrid, 256, 0, st>>>(SP, verts, faces, F, (const ViewRec*)views_out, NA, w.ctr, C, FragBg{})));
-  MR_CHECK_LAUNCH("k_bin_rect_world");
+  if ((rc = launch_bin_rect_world(SP, rgrid, verts, faces, F, views_out, NA, w.ctr, C, FragBg{}, st))) return rc;
   if ((rc = launch_bin_view(SP, w, g, N, nullptr, nullptr, F, true, st))) return rc;
   launch_raster_sil(P, g, N, st);
   MR_CHECK_LAUNCH("k_raster_kp (silhouette)");
   return MR_OK;
+}
+
+// The modular backwards' parameters from the settings; the upstream gradient pointers are the caller's.
+static RasterBwdParams make_raster_bwd(const mr_raster_settings_t* s, int64_t N, const float* fv, float* gfv) {
+  RasterBwdParams P;
+  memset(&P, 0, sizeof(P));
+  P.N = (int)N; P.H = s->H; P.W = s->W; P.NBX = ceil_div(s->W, MR_BT); P.K = s->faces_per_pixel;
+  P.persp = s->perspective_correct; P.clipb = s->clip_barycentric_coords;
+  P.cull = s->cull_backfaces; P.clipz = s->clip_z != 0; P.zc = s->z_clip_value;
+  P.blur = s->blur_radius; P.bbox_pad = sqrtf(s->blur_radius);
+  P.fv = fv; P.gfv = gfv;
+  return P;
 }
 
 int32_t mr_soft_silhouette_backward(const float* face_verts, int64_t N, int64_t F, const mr_raster_settings_t* s,
@@ -490,15 +526,11 @@ int32_t mr_soft_silhouette_backward(const float* face_verts, int64_t N, int64_t 
   if (hipMemsetAsync(grad_face_verts, 0, sizeof(float) * 9 * (size_t)Fb, st) != hipSuccess)
     return set_err(MR_ELAUNCH, "memset failed");
   BinGeom g = bin_geom(s->H, s->W, N, Fb, s->max_faces_per_bin);
-  RasterWS w = carve_raster_ws((void*)ws, N, Fb, s->H, s->W, g);
+  RasterWS w = carve_raster_ws((void*)ws, N, Fb, g);
   SilWS sw = carve_sil((void*)ws, w.bytes, N * (int64_t)g.T, K);
   SilBwdParams P;
   memset(&P, 0, sizeof(P));
-  P.R.N = (int)N; P.R.H = s->H; P.R.W = s->W; P.R.NBX = ceil_div(s->W, MR_BT); P.R.K = K;
-  P.R.persp = s->perspective_correct; P.R.clipb = s->clip_barycentric_coords;
-  P.R.cull = s->cull_backfaces; P.R.clipz = s->clip_z != 0; P.R.zc = s->z_clip_value;
-  P.R.blur = s->blur_radius; P.R.bbox_pad = sqrtf(s->blur_radius);
-  P.R.fv = face_verts; P.R.gfv = grad_face_verts;
+  P.R = make_raster_bwd(s, N, face_verts, grad_face_verts);
   P.T = g.T; P.TX = g.TX; P.isig = 1.0f / sigma;
   P.ctr = w.ctr; P.stile = w.stile; P.sent = sw.sent; P.spix = sw.spix;
   P.grad_rgba = grad_rgba;
@@ -520,12 +552,8 @@ int32_t mr_rasterize_meshes_backward(const float* fv, const int64_t* p2f, const 
   if (Ftot > 0 && hipMemsetAsync(gfv, 0, sizeof(float) * 9 * (size_t)Ftot, st) != hipSuccess)
     return set_err(MR_ELAUNCH, "memset failed");
   if (Ftot == 0 || (!gz && !gb && !gd)) return MR_OK;  // NULL gradients are zero
-  RasterBwdParams P;
-  P.N = (int)N; P.H = s->H; P.W = s->W; P.NBX = ceil_div(s->W, MR_BT); P.K = s->faces_per_pixel;
-  P.persp = s->perspective_correct; P.clipb = s->clip_barycentric_coords;
-  P.cull = s->cull_backfaces; P.clipz = s->clip_z != 0; P.zc = s->z_clip_value;
-  P.blur = s->blur_radius; P.bbox_pad = sqrtf(s->blur_radius);
-  P.fv = fv; P.p2f = p2f; P.gz = gz; P.gb = gb; P.gd = gd; P.gfv = gfv;
+  RasterBwdParams P = make_raster_bwd(s, N, fv, gfv);
+  P.p2f = p2f; P.gz = gz; P.gb = gb; P.gd = gd;
   const int64_t nslots = N * (int64_t)s->H * s->W * s->faces_per_pixel;
   MR_TIMED(KID_RASTER_BWD, st, (k_raster_bwd_slots<<<(unsigned)((nslots + 255) / 256), 256, 0, st>>>(P, nslots)));
   MR_CHECK_LAUNCH("k_raster_bwd");
@@ -591,29 +619,7 @@ int32_t mr_project_faces_meshes_backward(const float* verts, int64_t V, const in
   return MR_OK;
 }
 
-// OpenCV pose -> view records, and the conversion's chain rule (one thread per output float).
-__global__ void __launch_bounds__(256) k_views_from_opencv(const float* __restrict__ R, int64_t sR,
-                                                           const float* __restrict__ t, int64_t sT,
-                                                           const float* __restrict__ intr, int64_t sI, int64_t N,
-                                                           float* __restrict__ views) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N * 16) return;
-  const int64_t n = i >> 4;
-  const int k = (int)(i & 15);
-  float v;
-  if (k < 9) {  // R_p3d[a][b] = R_cv[b][a] * s[b], s = (-1, -1, 1)
-    const int a = k / 3, b = k - 3 * a;
-    v = R[n * sR + 3 * b + a];
-    if (b < 2) v = -v;
-  } else if (k < 12) {
-    v = t[n * sT + (k - 9)];
-    if (k < 11) v = -v;
-  } else {
-    v = intr[n * sI + (k - 12)];
-  }
-  views[i] = v;
-}
-
+// The chain rule of the OpenCV pose conversion (cv_view_elem), one thread per output float.
 __global__ void __launch_bounds__(256) k_view_grads_to_opencv(const float* __restrict__ g, int64_t N,
                                                               float* __restrict__ gR, float* __restrict__ gt) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -633,13 +639,9 @@ __global__ void __launch_bounds__(256) k_view_grads_to_opencv(const float* __res
 int32_t mr_views_from_opencv(const float* R_cv, int64_t R_stride, const float* t_cv, int64_t t_stride,
                              const float* intr, int64_t intr_stride, int64_t N, mr_view_t* views, void* stream) {
   if (N <= 0 || N > 65535) return set_err(MR_EINVAL, "N out of range");
-  if (!R_cv || !t_cv || !intr || !views) return set_err(MR_EINVAL, "NULL argument");
-  if (R_stride < 0 || t_stride < 0 || intr_stride < 0) return set_err(MR_EINVAL, "negative stride");
-  hipStream_t st = (hipStream_t)stream;
-  k_views_from_opencv<<<ceil_div(N * 16, 256), 256, 0, st>>>(R_cv, R_stride, t_cv, t_stride, intr, intr_stride, N,
-                                                            (float*)views);
-  MR_CHECK_LAUNCH("k_views_from_opencv");
-  return MR_OK;
+  CvPoses C;
+  const int rc = cv_poses(&C, R_cv, R_stride, t_cv, t_stride, intr, intr_stride, views, 1);
+  return rc ? rc : launch_views_from_cv(C, N, (hipStream_t)stream);
 }
 
 int32_t mr_view_grads_to_opencv(const float* grad_views, int64_t N, float* grad_R_cv, float* grad_t_cv,
@@ -720,50 +722,24 @@ static int check_mesh(const mr_mesh_t* m, const mr_shade_params_t* sp) {
 
 size_t mr_render_workspace(int64_t N, int64_t F, int32_t H, int32_t W, int32_t max_faces_per_bin) {
   BinGeom g = bin_geom(H, W, N, N * F, max_faces_per_bin);
-  return carve_raster_ws(nullptr, N, N * F, H, W, g, F).bytes;
+  return carve_raster_ws(nullptr, N, N * F, g, F).bytes;
 }
 size_t mr_render_workspace_meshes(int64_t N, int64_t F, int32_t H, int32_t W, int32_t max_faces_per_bin) {
   BinGeom g = bin_geom(H, W, N, F, max_faces_per_bin);
-  return carve_raster_ws(nullptr, N, F, H, W, g, F).bytes;
+  return carve_raster_ws(nullptr, N, F, g, F).bytes;
 }
 
-static int32_t render_forward(const mr_mesh_t* m, const mr_view_t* views, int64_t N, const float* cc, int64_t ncc,
-                              const mr_raster_settings_t* s, const mr_shade_params_t* sp, float* depth, float* sil,
-                              float* rgb, int32_t* p2f32, void* ws, size_t ws_bytes, void* stream, const CvPoses& C);
-int32_t mr_render_forward(const mr_mesh_t* m, const mr_view_t* views, int64_t N, const float* cc, int64_t ncc,
-                          const mr_raster_settings_t* s, const mr_shade_params_t* sp, float* depth, float* sil,
-                          float* rgb, int32_t* p2f32, void* ws, size_t ws_bytes, void* stream) {
-  CvPoses C;
-  memset(&C, 0, sizeof(C));
-  return render_forward(m, views, N, cc, ncc, s, sp, depth, sil, rgb, p2f32, ws, ws_bytes, stream, C);
-}
-int32_t mr_render_forward_opencv(const mr_mesh_t* m, const mr_opencv_poses_t* poses, mr_view_t* views_out, int64_t N,
-                                 const float* cc, int64_t ncc, const mr_raster_settings_t* s,
-                                 const mr_shade_params_t* sp, float* depth, float* sil, float* rgb, int32_t* p2f32,
-                                 void* ws, size_t ws_bytes, void* stream) {
-  if (!poses || !poses->R || !poses->t || !poses->intr || !views_out) return set_err(MR_EINVAL, "NULL pose argument");
-  if (poses->R_stride < 0 || poses->t_stride < 0 || poses->intr_stride < 0) return set_err(MR_EINVAL, "negative stride");
-  CvPoses C;
-  C.R = poses->R; C.sR = poses->R_stride; C.t = poses->t; C.sT = poses->t_stride;
-  C.intr = poses->intr; C.sI = poses->intr_stride; C.out = (float*)views_out;
-  C.opencv = 1;
-  return render_forward(m, views_out, N, cc, ncc, s, sp, depth, sil, rgb, p2f32, ws, ws_bytes, stream, C);
-}
-int32_t mr_render_forward_poses(const mr_mesh_t* m, const mr_poses_t* poses, mr_view_t* views_out, int64_t N,
-                                const float* cc, int64_t ncc, const mr_raster_settings_t* s,
-                                const mr_shade_params_t* sp, float* depth, float* sil, float* rgb, int32_t* p2f32,
-                                void* ws, size_t ws_bytes, void* stream) {
-  if (!poses || !poses->R || !poses->T || !poses->intr || !views_out) return set_err(MR_EINVAL, "NULL pose argument");
-  if (poses->R_stride < 0 || poses->T_stride < 0 || poses->intr_stride < 0) return set_err(MR_EINVAL, "negative stride");
-  CvPoses C;
-  C.R = poses->R; C.sR = poses->R_stride; C.t = poses->T; C.sT = poses->T_stride;
-  C.intr = poses->intr; C.sI = poses->intr_stride; C.out = (float*)views_out;
-  C.opencv = 0;
-  return render_forward(m, views_out, N, cc, ncc, s, sp, depth, sil, rgb, p2f32, ws, ws_bytes, stream, C);
-}
-static int32_t render_forward(const mr_mesh_t* m, const mr_view_t* views, int64_t N, const float* cc, int64_t ncc,
-                              const mr_raster_settings_t* s, const mr_shade_params_t* sp, float* depth, float* sil,
-                              float* rgb, int32_t* p2f32, void* ws, size_t ws_bytes, void* stream, const CvPoses& C) {
+// One fused render call, as mr_render_forward* and mr_render_reshade both start: the arguments checked, the
+// batch geometry, the carved workspace and the raster / shade parameters (ShadeRec slot and outputs set).
+struct RenderCall {
+  int64_t NF, maxvf;  // face records of the batch; most faces of one view
+  BinGeom g;
+  RasterWS w;
+  FwdParams P;
+};
+static int render_call(RenderCall& c, const mr_mesh_t* m, const mr_view_t* views, int64_t N, const float* cc,
+                       int64_t ncc, const mr_raster_settings_t* s, const mr_shade_params_t* sp, float* depth,
+                       float* sil, float* rgb, int32_t* p2f32, void* ws, size_t ws_bytes) {
   int rc = check_settings(s);
   if (rc) return rc;
   rc = check_mesh(m, sp);
@@ -773,33 +749,47 @@ static int32_t render_forward(const mr_mesh_t* m, const mr_view_t* views, int64_
   if (N <= 0 || N > 65535) return set_err(MR_EINVAL, "N out of range");
   // record ids: n*F + f for one shared mesh; the union face id for distinct meshes
   const bool multi = m->view_face_first != nullptr;
-  const int64_t NF = multi ? m->F : N * m->F, maxvf = multi ? m->max_view_faces : m->F;
-  if (multi && (!m->view_face_count || maxvf <= 0)) return set_err(MR_EINVAL, "distinct meshes: face ranges missing");
-  if (NF >= (1ll << 31)) return set_err(MR_EUNSUPPORTED, "N*F >= 2^31");
+  c.NF = multi ? m->F : N * m->F;
+  c.maxvf = multi ? m->max_view_faces : m->F;
+  if (multi && (!m->view_face_count || c.maxvf <= 0)) return set_err(MR_EINVAL, "distinct meshes: face ranges missing");
+  if (c.NF >= (1ll << 31)) return set_err(MR_EUNSUPPORTED, "N*F >= 2^31");
   if ((int64_t)N * s->H * s->W >= (1ll << 31)) return set_err(MR_EUNSUPPORTED, "N*H*W >= 2^31");
   if (!views) return set_err(MR_EINVAL, "NULL views");
   if ((sp->out_flags & MR_OUT_DEPTH) && !depth) return set_err(MR_EINVAL, "depth output NULL");
   if ((sp->out_flags & MR_OUT_SIL) && !sil) return set_err(MR_EINVAL, "silhouette output NULL");
   if ((sp->out_flags & MR_OUT_RGB) && !rgb) return set_err(MR_EINVAL, "rgb output NULL");
   if (sp->light_kind == 0 && (!cc || (ncc != 1 && ncc != N))) return set_err(MR_EINVAL, "camera centres");
+  c.g = bin_geom(s->H, s->W, N, c.NF, s->max_faces_per_bin);
+  c.w = carve_raster_ws(ws, N, c.NF, c.g, m->F);
+  if (ws_bytes < c.w.bytes) return set_err(MR_EWORKSPACE, "workspace too small: %zu < %zu", ws_bytes, c.w.bytes);
+  if (!ws) return set_err(MR_EINVAL, "NULL workspace");
+  c.P = make_fwd(s, c.g, c.w, N, m->view_face_first, multi ? 0 : m->F, c.NF);
+  c.P.view_count = m->view_face_count;
+  c.P.S = make_shade(m, sp, cc, ncc);
+  c.P.srec = c.w.srec + (size_t)srec_slot(sp) * m->F;
+  c.P.out_flags = sp->out_flags;
+  c.P.depth = depth;
+  c.P.sil = sil;
+  c.P.rgb = rgb;
+  c.P.p2f32 = p2f32;
+  return MR_OK;
+}
+
+// C.R non-NULL: the view records come from the pose arrays (written to C.out = views by the first launch)
+static int32_t render_forward(const mr_mesh_t* m, const mr_view_t* views, int64_t N, const float* cc, int64_t ncc,
+                              const mr_raster_settings_t* s, const mr_shade_params_t* sp, float* depth, float* sil,
+                              float* rgb, int32_t* p2f32, void* ws, size_t ws_bytes, void* stream, const CvPoses& C) {
+  RenderCall c;
+  int rc = render_call(c, m, views, N, cc, ncc, s, sp, depth, sil, rgb, p2f32, ws, ws_bytes);
+  if (rc) return rc;
+  const BinGeom& g = c.g;
+  const RasterWS& w = c.w;
+  FwdParams& P = c.P;
   hipStream_t st = (hipStream_t)stream;
-  BinGeom g = bin_geom(s->H, s->W, N, NF, s->max_faces_per_bin);
-  RasterWS w = carve_raster_ws(ws, N, NF, s->H, s->W, g, m->F);
-  if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "workspace too small: %zu < %zu", ws_bytes, w.bytes);
   SetupParams SP = make_setup(s, g, w);
-  SP.NF = NF;
+  SP.NF = c.NF;
   SP.vff = m->view_face_first;
-  FwdParams P = make_fwd(s, g, w, N, m->view_face_first, multi ? 0 : m->F, NF);
-  P.view_count = m->view_face_count;
-  P.S = make_shade(m, sp, cc, ncc);
-  P.srec = w.srec + (size_t)srec_slot(sp) * m->F;
-  P.out_flags = sp->out_flags;
-  P.depth = depth;
-  P.sil = sil;
-  P.rgb = rgb;
-  P.p2f32 = p2f32;
-  const bool vpath = view_binning(g, N, NF);
-  const int64_t nzero = (int64_t)(zero_bytes(N, g, vpath) / sizeof(int));
+  const bool vpath = view_binning(g, N, c.NF), ch4 = sp->rgb_channels == 4;
   // normals computed here (the mesh's vnormals_out) or passed in (vnormals)
   const int64_t vb = (sp->light_kind == 0 && m->vnormals_out) ? ceil_div(m->V, 256) : 0;
   if (vb) {
@@ -821,83 +811,77 @@ static int32_t render_forward(const mr_mesh_t* m, const mr_view_t* views, int64_
     NA.nzero4 = (nacc + 1) / 2;
     NA.zero4b = (float4*)w.gflt;
     NA.nzero4b = (nacc + 3) / 4;
-    const int64_t bx = std::max<int64_t>(ceil_div(maxvf, 256), ceil_div(m->V, 256));
+    const int64_t bx = std::max<int64_t>(ceil_div(c.maxvf, 256), ceil_div(m->V, 256));
     dim3 rgrid((unsigned)(bx > 0 ? bx : 1), (unsigned)N + 1);  // row 0: normals + counter clear
-    if (SP.clipz) MR_TIMED(KID_BIN_RECT, st, (k_bin_rect_world<true><<<rgrid, 256, 0, st>>>(SP, m->verts, m->faces, m->F, (const ViewRec*)views, NA, w.ctr, C, FragBg{})));
-    else MR_TIMED(KID_BIN_RECT, st, (k_bin_rect_world<false><<<rgrid, 256, 0, st>>>(SP, m->verts, m->faces, m->F, (const ViewRec*)views, NA, w.ctr, C, FragBg{})));
-    MR_CHECK_LAUNCH("k_bin_rect_world");
-    if (sp->rgb_channels == 4) {
-      if ((rc = launch_bin_view<1, 4>(SP, w, g, N, m->view_face_first, m->view_face_count, m->F, false, st, &P.S, &P))) return rc;
-      return launch_raster_and_shade<1, 4>(P, g, N, st, s->clip_z != 0);
-    }
-    if ((rc = launch_bin_view<1, 3>(SP, w, g, N, m->view_face_first, m->view_face_count, m->F, false, st, &P.S, &P))) return rc;
-    return launch_raster_and_shade<1, 3>(P, g, N, st, s->clip_z != 0);
+    if ((rc = launch_bin_rect_world(SP, rgrid, m->verts, m->faces, m->F, views, NA, w.ctr, C, FragBg{}, st))) return rc;
+    rc = ch4 ? launch_bin_view<1, 4>(SP, w, g, N, m->view_face_first, m->view_face_count, m->F, false, st, &P.S, &P)
+             : launch_bin_view<1, 3>(SP, w, g, N, m->view_face_first, m->view_face_count, m->F, false, st, &P.S, &P);
+    if (rc) return rc;
+  } else {
+    if (hipMemsetAsync(w.gfix, 0, sizeof(unsigned long long) * 27 * (size_t)m->F, st) != hipSuccess ||
+        hipMemsetAsync(w.gflt, 0, sizeof(float) * 27 * (size_t)m->F, st) != hipSuccess)
+      return set_err(MR_ELAUNCH, "memset failed");
+    if (C.R && (rc = launch_views_from_cv(C, N, st))) return rc;  // count -> scan path: the view records first
+    const int64_t nzero = (int64_t)(zero_bytes(N, g, vpath) / sizeof(int));
+    MR_TIMED(KID_SETUP, st, (k_setup_zero<<<(unsigned)(vb + ceil_div(nzero, 1024)), 256, 0, st>>>(m->verts, m->V, m->faces, m->vadj_ptr, m->vadj, m->vnormals_out, m->vraw_out, vb, w.ctr, nzero)));
+    MR_CHECK_LAUNCH("k_setup_zero");
+    const int fpt = MR_BIN_FPT;
+    dim3 sgrid(ceil_div(c.maxvf, 256 * fpt), (unsigned)N);
+    dim3 fgrid(ceil_div(m->F, 256 * fpt), (unsigned)N + 1);  // + the ShadeRec row (every face of the mesh(es))
+    const bool lds = g.T <= MR_LDS_HIST;
+    const size_t shm = lds ? sizeof(int) * (size_t)g.T : 0;
+    if (lds)
+      MR_TIMED(KID_BIN_COUNT, st, (k_bin_count_world<true><<<sgrid, 256, shm, st>>>(SP, m->verts, m->faces, m->F, (const ViewRec*)views, fpt)));
+    else
+      MR_TIMED(KID_BIN_COUNT, st, (k_bin_count_world<false><<<sgrid, 256, 0, st>>>(SP, m->verts, m->faces, m->F, (const ViewRec*)views, fpt)));
+    MR_CHECK_LAUNCH("k_bin_count_world");
+    if ((rc = launch_scan(w, N, g, m->view_face_count, m->F, st))) return rc;
+    if (lds)
+      MR_TIMED(KID_BIN_FILL, st, (k_bin_fill_world<true><<<fgrid, 256, shm, st>>>(SP, m->F, fpt, (int)N, P.S, (ShadeRec*)P.srec)));
+    else
+      MR_TIMED(KID_BIN_FILL, st, (k_bin_fill_world<false><<<fgrid, 256, 0, st>>>(SP, m->F, fpt, (int)N, P.S, (ShadeRec*)P.srec)));
+    MR_CHECK_LAUNCH("k_bin_fill_world");
   }
-  if (hipMemsetAsync(w.gfix, 0, sizeof(unsigned long long) * 27 * (size_t)m->F, st) != hipSuccess ||
-      hipMemsetAsync(w.gflt, 0, sizeof(float) * 27 * (size_t)m->F, st) != hipSuccess)
-    return set_err(MR_ELAUNCH, "memset failed");
-  if (C.R) {  // count -> scan path: the view records first
-    if (C.opencv) {
-      k_views_from_opencv<<<ceil_div(N * 16, 256), 256, 0, st>>>(C.R, C.sR, C.t, C.sT, C.intr, C.sI, N, C.out);
-      MR_CHECK_LAUNCH("k_views_from_opencv");
-    } else {
-      k_views_from_cv<<<ceil_div(N * 16, 256), 256, 0, st>>>(C, N);
-      MR_CHECK_LAUNCH("k_views_from_cv");
-    }
-  }
-  MR_TIMED(KID_SETUP, st, (k_setup_zero<<<(unsigned)(vb + ceil_div(nzero, 1024)), 256, 0, st>>>(m->verts, m->V, m->faces, m->vadj_ptr, m->vadj, m->vnormals_out, m->vraw_out, vb, w.ctr, nzero)));
-  MR_CHECK_LAUNCH("k_setup_zero");
-  const int fpt = MR_BIN_FPT;
-  dim3 sgrid(ceil_div(maxvf, 256 * fpt), (unsigned)N);
-  dim3 fgrid(ceil_div(m->F, 256 * fpt), (unsigned)N + 1);  // + the ShadeRec row (every face of the mesh(es))
-  const bool lds = g.T <= MR_LDS_HIST;
-  const size_t shm = lds ? sizeof(int) * (size_t)g.T : 0;
-  if (lds)
-    MR_TIMED(KID_BIN_COUNT, st, (k_bin_count_world<true><<<sgrid, 256, shm, st>>>(SP, m->verts, m->faces, m->F, (const ViewRec*)views, fpt)));
-  else
-    MR_TIMED(KID_BIN_COUNT, st, (k_bin_count_world<false><<<sgrid, 256, 0, st>>>(SP, m->verts, m->faces, m->F, (const ViewRec*)views, fpt)));
-  MR_CHECK_LAUNCH("k_bin_count_world");
-  if ((rc = launch_scan(w, N, g, m->view_face_count, m->F, st))) return rc;
-  if (lds)
-    MR_TIMED(KID_BIN_FILL, st, (k_bin_fill_world<true><<<fgrid, 256, shm, st>>>(SP, m->F, fpt, (int)N, P.S, (ShadeRec*)P.srec)));
-  else
-    MR_TIMED(KID_BIN_FILL, st, (k_bin_fill_world<false><<<fgrid, 256, 0, st>>>(SP, m->F, fpt, (int)N, P.S, (ShadeRec*)P.srec)));
-  MR_CHECK_LAUNCH("k_bin_fill_world");
-  if (sp->rgb_channels == 4) return launch_raster_and_shade<1, 4>(P, g, N, st, s->clip_z != 0);
-  return launch_raster_and_shade<1, 3>(P, g, N, st, s->clip_z != 0);
+  return ch4 ? launch_raster_and_shade<1, 4>(P, g, N, st, s->clip_z != 0)
+             : launch_raster_and_shade<1, 3>(P, g, N, st, s->clip_z != 0);
+}
+
+int32_t mr_render_forward(const mr_mesh_t* m, const mr_view_t* views, int64_t N, const float* cc, int64_t ncc,
+                          const mr_raster_settings_t* s, const mr_shade_params_t* sp, float* depth, float* sil,
+                          float* rgb, int32_t* p2f32, void* ws, size_t ws_bytes, void* stream) {
+  CvPoses C;
+  memset(&C, 0, sizeof(C));
+  return render_forward(m, views, N, cc, ncc, s, sp, depth, sil, rgb, p2f32, ws, ws_bytes, stream, C);
+}
+int32_t mr_render_forward_opencv(const mr_mesh_t* m, const mr_opencv_poses_t* poses, mr_view_t* views_out, int64_t N,
+                                 const float* cc, int64_t ncc, const mr_raster_settings_t* s,
+                                 const mr_shade_params_t* sp, float* depth, float* sil, float* rgb, int32_t* p2f32,
+                                 void* ws, size_t ws_bytes, void* stream) {
+  if (!poses) return set_err(MR_EINVAL, "NULL pose argument");
+  CvPoses C;
+  const int rc = cv_poses(&C, poses->R, poses->R_stride, poses->t, poses->t_stride, poses->intr, poses->intr_stride,
+                          views_out, 1);
+  return rc ? rc : render_forward(m, views_out, N, cc, ncc, s, sp, depth, sil, rgb, p2f32, ws, ws_bytes, stream, C);
+}
+int32_t mr_render_forward_poses(const mr_mesh_t* m, const mr_poses_t* poses, mr_view_t* views_out, int64_t N,
+                                const float* cc, int64_t ncc, const mr_raster_settings_t* s,
+                                const mr_shade_params_t* sp, float* depth, float* sil, float* rgb, int32_t* p2f32,
+                                void* ws, size_t ws_bytes, void* stream) {
+  if (!poses) return set_err(MR_EINVAL, "NULL pose argument");
+  CvPoses C;
+  const int rc = cv_poses(&C, poses->R, poses->R_stride, poses->T, poses->T_stride, poses->intr, poses->intr_stride,
+                          views_out, 0);
+  return rc ? rc : render_forward(m, views_out, N, cc, ncc, s, sp, depth, sil, rgb, p2f32, ws, ws_bytes, stream, C);
 }
 
 int32_t mr_render_reshade(const mr_mesh_t* m, const mr_view_t* views, int64_t N, const float* cc, int64_t ncc,
                           const mr_raster_settings_t* s, const mr_shade_params_t* sp, float* depth, float* sil,
                           float* rgb, int32_t* p2f32, void* ws, size_t ws_bytes, void* stream) {
-  int rc = check_settings(s);
+  RenderCall c;
+  const int rc = render_call(c, m, views, N, cc, ncc, s, sp, depth, sil, rgb, p2f32, ws, ws_bytes);
   if (rc) return rc;
-  rc = check_mesh(m, sp);
-  if (rc) return rc;
-  if (s->faces_per_pixel != 1) return set_err(MR_EUNSUPPORTED, "the fused render path is K = 1");
-  if (sp->out_flags & MR_OUT_HARD) return set_err(MR_EUNSUPPORTED, "hard_rgb_blend runs on the fragment-shader path");
-  if (N <= 0 || N > 65535) return set_err(MR_EINVAL, "N out of range");
-  const bool multi = m->view_face_first != nullptr;
-  const int64_t NF = multi ? m->F : N * m->F;
-  if ((int64_t)N * s->H * s->W >= (1ll << 31)) return set_err(MR_EUNSUPPORTED, "N*H*W >= 2^31");
-  if (!views || !ws) return set_err(MR_EINVAL, "NULL views / workspace");
-  if ((sp->out_flags & MR_OUT_DEPTH) && !depth) return set_err(MR_EINVAL, "depth output NULL");
-  if ((sp->out_flags & MR_OUT_SIL) && !sil) return set_err(MR_EINVAL, "silhouette output NULL");
-  if ((sp->out_flags & MR_OUT_RGB) && !rgb) return set_err(MR_EINVAL, "rgb output NULL");
-  if (sp->light_kind == 0 && (!cc || (ncc != 1 && ncc != N))) return set_err(MR_EINVAL, "camera centres");
+  FwdParams& P = c.P;
   hipStream_t st = (hipStream_t)stream;
-  BinGeom g = bin_geom(s->H, s->W, N, NF, s->max_faces_per_bin);
-  RasterWS w = carve_raster_ws(ws, N, NF, s->H, s->W, g, m->F);
-  if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "workspace too small: %zu < %zu", ws_bytes, w.bytes);
-  FwdParams P = make_fwd(s, g, w, N, m->view_face_first, multi ? 0 : m->F, NF);
-  P.view_count = m->view_face_count;
-  P.S = make_shade(m, sp, cc, ncc);
-  P.srec = w.srec + (size_t)srec_slot(sp) * m->F;
-  P.out_flags = sp->out_flags;
-  P.depth = depth;
-  P.sil = sil;
-  P.rgb = rgb;
-  P.p2f32 = p2f32;
   // this call's vertex normals (as the forward's first launch), when its shading reads them: Phong RGB only
   if (sp->light_kind == 0 && m->vnormals_out && (sp->out_flags & MR_OUT_RGB)) {
     if (!m->vraw_out) return set_err(MR_EINVAL, "vnormals_out without vraw_out");
@@ -907,27 +891,8 @@ int32_t mr_render_reshade(const mr_mesh_t* m, const mr_view_t* views, int64_t N,
   }
   MR_TIMED(KID_SHADE_REC, st, (k_shade_rec<<<ceil_div(m->F, 256), 256, 0, st>>>(P.S, m->F, (ShadeRec*)P.srec)));
   MR_CHECK_LAUNCH("k_shade_rec");
-  static int fg3 = 0, fg4 = 0, sg3 = 0, sg4 = 0;
-  const int64_t slots_cap = N * (int64_t)g.T;
-  auto shade_grid = [&](int gr) {
-    int sg = (int)(slots_cap / 4 + 1 < gr ? slots_cap / 4 + 1 : gr);
-    return (sg + 7) / 8 * 8;  // XCD-partitioned slot ranges
-  };
-  if (sp->rgb_channels == 4) {
-    if (!fg4) fg4 = resident_grid(k_fill<1, 4>, 256, 8);
-    if (!sg4) sg4 = resident_grid(k_shade<1, 4>, 256, 6);
-    MR_TIMED(KID_FILL_FRAG, st, (k_fill<1, 4><<<fg4, 256, 0, st>>>(P)));
-    MR_CHECK_LAUNCH("k_fill");
-    MR_TIMED(KID_SHADE_RENDER, st, (k_shade<1, 4><<<shade_grid(sg4), 256, 0, st>>>(P)));
-  } else {
-    if (!fg3) fg3 = resident_grid(k_fill<1, 3>, 256, 8);
-    if (!sg3) sg3 = resident_grid(k_shade<1, 3>, 256, 6);
-    MR_TIMED(KID_FILL_FRAG, st, (k_fill<1, 3><<<fg3, 256, 0, st>>>(P)));
-    MR_CHECK_LAUNCH("k_fill");
-    MR_TIMED(KID_SHADE_RENDER, st, (k_shade<1, 3><<<shade_grid(sg3), 256, 0, st>>>(P)));
-  }
-  MR_CHECK_LAUNCH("k_shade");
-  return MR_OK;
+  const int64_t slots_cap = N * (int64_t)c.g.T;
+  return sp->rgb_channels == 4 ? launch_fill_and_shade<4>(P, slots_cap, st) : launch_fill_and_shade<3>(P, slots_cap, st);
 }
 
 size_t mr_render_backward_workspace(int64_t N, int64_t V, int64_t F, int32_t H, int32_t W) {
@@ -937,31 +902,7 @@ size_t mr_render_backward_workspace(int64_t N, int64_t V, int64_t F, int32_t H, 
   return off;
 }
 
-static int32_t render_backward(const mr_mesh_t* m, const float* vraw, const mr_view_t* views, int64_t N,
-                               const float* cc, int64_t ncc, const mr_raster_settings_t* s,
-                               const mr_shade_params_t* sp, const float* gD, const float* gS, const float* gRGB,
-                               const void* fws, void* bws, size_t bws_bytes, float* gverts, float* gviews,
-                               float* gRcv, float* gtcv, float* gcol, void* stream);
-
-int32_t mr_render_backward(const mr_mesh_t* m, const float* vraw, const mr_view_t* views, int64_t N, const float* cc,
-                           int64_t ncc, const mr_raster_settings_t* s, const mr_shade_params_t* sp,
-                           const float* gD, const float* gS, const float* gRGB, const void* fws, void* bws,
-                           size_t bws_bytes, float* gverts, float* gviews, float* gcol, void* stream) {
-  if (!gviews) return set_err(MR_EINVAL, "NULL argument");
-  return render_backward(m, vraw, views, N, cc, ncc, s, sp, gD, gS, gRGB, fws, bws, bws_bytes, gverts, gviews,
-                         nullptr, nullptr, gcol, stream);
-}
-
-int32_t mr_render_backward_opencv(const mr_mesh_t* m, const float* vraw, const mr_view_t* views, int64_t N,
-                                  const float* cc, int64_t ncc, const mr_raster_settings_t* s,
-                                  const mr_shade_params_t* sp, const float* gD, const float* gS, const float* gRGB,
-                                  const void* fws, void* bws, size_t bws_bytes, float* gverts, float* grad_R_cv,
-                                  float* grad_t_cv, float* gcol, void* stream) {
-  if (!grad_R_cv || !grad_t_cv) return set_err(MR_EINVAL, "NULL argument");
-  return render_backward(m, vraw, views, N, cc, ncc, s, sp, gD, gS, gRGB, fws, bws, bws_bytes, gverts, nullptr,
-                         grad_R_cv, grad_t_cv, gcol, stream);
-}
-
+// gviews, or gRcv and gtcv: the pose gradients as view-record rows or in the OpenCV convention
 static int32_t render_backward(const mr_mesh_t* m, const float* vraw, const mr_view_t* views, int64_t N,
                                const float* cc, int64_t ncc, const mr_raster_settings_t* s,
                                const mr_shade_params_t* sp, const float* gD, const float* gS, const float* gRGB,
@@ -983,23 +924,18 @@ static int32_t render_backward(const mr_mesh_t* m, const float* vraw, const mr_v
   const bool multi = m->view_face_first != nullptr;  // distinct meshes: record id = union face id
   const int64_t NF = multi ? m->F : N * m->F;
   BinGeom g = bin_geom(s->H, s->W, N, NF, s->max_faces_per_bin);
-  RasterWS w = carve_raster_ws((void*)fws, N, NF, s->H, s->W, g, m->F);
+  RasterWS w = carve_raster_ws((void*)fws, N, NF, g, m->F);
   const bool vcol = m->tex_kind == 1;
   const int ACC = vcol ? 27 : 18;
   const int64_t NT = N * (int64_t)g.T;
-  char* b = (char*)bws;
-  size_t off = 0;
-  float* gnu = (float*)(b + off);
-  off = align_up(off + sizeof(float) * 3 * (size_t)m->V, 256);
-  float* rt_part = (float*)(b + off);
+  float* gnu = (float*)bws;
+  float* rt_part = (float*)((char*)bws + align_up(sizeof(float) * 3 * (size_t)m->V, 256));
   // the per-face totals (fixed point + float remainder) live in the forward's workspace, which the
   // forward cleared; a second backward over the same forward (MR_GRAD_ROWS_CLEARED not set) clears
   // them again
-  unsigned long long* gfix = w.gfix;
-  float* gface = w.gflt;
   if (!(sp->out_flags & MR_GRAD_ROWS_CLEARED) &&
-      (hipMemsetAsync(gfix, 0, sizeof(unsigned long long) * ACC * (size_t)m->F, st) != hipSuccess ||
-       hipMemsetAsync(gface, 0, sizeof(float) * ACC * (size_t)m->F, st) != hipSuccess))
+      (hipMemsetAsync(w.gfix, 0, sizeof(unsigned long long) * ACC * (size_t)m->F, st) != hipSuccess ||
+       hipMemsetAsync(w.gflt, 0, sizeof(float) * ACC * (size_t)m->F, st) != hipSuccess))
     return set_err(MR_ELAUNCH, "memset failed");
   RenderBwdParams P;
   memset(&P, 0, sizeof(P));
@@ -1023,30 +959,13 @@ static int32_t render_backward(const mr_mesh_t* m, const float* vraw, const mr_v
   P.crec = w.crec;
   P.zc = s->z_clip_value;
   P.views = (const ViewRec*)views;
-  P.gfix = gfix;
-  P.gface = gface;
+  P.gfix = w.gfix;
+  P.gface = w.gflt;
   P.fflag = w.ctr + CTR_FLT;
   P.rt_part = rt_part;
   P.frec = w.frec;
   P.sgrp = w.sgrp;
   P.sgpix = w.sgpix;
-#ifndef MR_BWD_GRID_MUL
-#define MR_BWD_GRID_MUL 1
-#endif
-  auto cap = [&](int gr) {  // enough waves for every tile, a multiple of 8 (XCD-partitioned slot ranges)
-    gr *= MR_BWD_GRID_MUL;
-    const int c = (int)(NT / 4 + 1 < gr ? NT / 4 + 1 : gr);
-    return (c + 7) / 8 * 8;
-  };
-  static int f18 = 0, f27 = 0, f18c = 0, f27c = 0, g18 = 0, g27 = 0, g18c = 0, g27c = 0;
-  if (!f18) f18 = resident_grid(k_bwd_fused<18, false>, 256, 3);
-  if (!f27) f27 = resident_grid(k_bwd_fused<27, false>, 256, 2);
-  if (!f18c) f18c = resident_grid(k_bwd_fused<18, true>, 256, 3);
-  if (!f27c) f27c = resident_grid(k_bwd_fused<27, true>, 256, 2);
-  if (!g18) g18 = resident_grid(k_bwd_fused<18, false, true>, 256, 4);
-  if (!g27) g27 = resident_grid(k_bwd_fused<27, false, true>, 256, 4);
-  if (!g18c) g18c = resident_grid(k_bwd_fused<18, true, true>, 256, 4);
-  if (!g27c) g27c = resident_grid(k_bwd_fused<27, true, true>, 256, 4);
   // no RGB gradient (a depth / silhouette render's backward): the geometry-only instantiation
   const bool geo = P.gRGB == nullptr;
   // the drop-in Phong render (UV map with an 8-bit copy, point light, RGB, relu depth): the specialised one
@@ -1055,47 +974,47 @@ static int32_t render_backward(const mr_mesh_t* m, const float* vraw, const mr_v
 #endif
   const bool spec = MR_BWD_SPEC && !geo && !vcol && !s->clip_z && m->tex_kind == 2 && m->tex_u8 && m->tex_lut &&
                     sp->light_kind == 0 && sp->rgb_channels == 3 && !(sp->out_flags & (MR_OUT_ZBUF | MR_OUT_SIL_RGBA));
-  static int f18s = 0;
-  if (!f18s) f18s = resident_grid(k_bwd_fused<18, false, false, 1>, 256, 3);
-  if (s->clip_z) {
-    if (geo) {
-      if (vcol) MR_TIMED(KID_BWD_FUSED, st, (k_bwd_fused<27, true, true><<<cap(g27c), 256, 0, st>>>(P)));
-      else MR_TIMED(KID_BWD_FUSED, st, (k_bwd_fused<18, true, true><<<cap(g18c), 256, 0, st>>>(P)));
-    } else if (vcol) MR_TIMED(KID_BWD_FUSED, st, (k_bwd_fused<27, true><<<cap(f27c), 256, 0, st>>>(P)));
-    else MR_TIMED(KID_BWD_FUSED, st, (k_bwd_fused<18, true><<<cap(f18c), 256, 0, st>>>(P)));
-  } else {
-    if (geo) {
-      if (vcol) MR_TIMED(KID_BWD_FUSED, st, (k_bwd_fused<27, false, true><<<cap(g27), 256, 0, st>>>(P)));
-      else MR_TIMED(KID_BWD_FUSED, st, (k_bwd_fused<18, false, true><<<cap(g18), 256, 0, st>>>(P)));
-    } else if (vcol) MR_TIMED(KID_BWD_FUSED, st, (k_bwd_fused<27, false><<<cap(f27), 256, 0, st>>>(P)));
-    else if (spec) MR_TIMED(KID_BWD_FUSED, st, (k_bwd_fused<18, false, false, 1><<<cap(f18s), 256, 0, st>>>(P)));
-    else MR_TIMED(KID_BWD_FUSED, st, (k_bwd_fused<18, false><<<cap(f18), 256, 0, st>>>(P)));
+  switch (spec ? 8 : (vcol ? 1 : 0) | (s->clip_z ? 2 : 0) | (geo ? 4 : 0)) {
+    case 0: rc = launch_bwd_fused<18, false>(P, NT, st); break;
+    case 1: rc = launch_bwd_fused<27, false>(P, NT, st); break;
+    case 2: rc = launch_bwd_fused<18, true>(P, NT, st); break;
+    case 3: rc = launch_bwd_fused<27, true>(P, NT, st); break;
+    case 4: rc = launch_bwd_fused<18, false, true>(P, NT, st); break;
+    case 5: rc = launch_bwd_fused<27, false, true>(P, NT, st); break;
+    case 6: rc = launch_bwd_fused<18, true, true>(P, NT, st); break;
+    case 7: rc = launch_bwd_fused<27, true, true>(P, NT, st); break;
+    default: rc = launch_bwd_fused<18, false, false, 1>(P, NT, st); break;
   }
-  MR_CHECK_LAUNCH("k_bwd_fused");
-  const int use_n = sp->light_kind == 0;
-  const int vb = ceil_div(m->V * MR_VL, 256);
+  if (rc) return rc;
+  VertexGradArgs A;
+  A.RR.part = rt_part; A.RR.vslot = w.vslot; A.RR.N = (int)N;
   // the forward's slot ranges: one per (view, band) on the per-view binning, one per view otherwise
-  const int bands = view_binning(g, N, NF) ? bin_bands(N, g) : 1;
-  RtReduce RR;
-  RR.part = rt_part; RR.vslot = w.vslot; RR.N = (int)N; RR.bands = bands;
-  RR.gviews = gviews; RR.gRcv = gRcv; RR.gtcv = gtcv;
-  const int vbw = ceil_div(m->V * MR_VL, MR_VGRAD_NT);  // vertex-gather workgroups of k_rt_vgrad_a / _b
-  if (!use_n) {  // no normal chain: the R/T reduction and the vertex gathers in one launch
-    if (vcol) MR_TIMED(KID_RT_VGRAD_B, st, (k_rt_vgrad_b<27><<<(unsigned)(N + vbw), MR_VGRAD_NT, 0, st>>>(RR, m->V, m->vadj_ptr, m->vadj, gfix, gface, P.fflag, gverts, gcol)));
-    else MR_TIMED(KID_RT_VGRAD_B, st, (k_rt_vgrad_b<18><<<(unsigned)(N + vbw), MR_VGRAD_NT, 0, st>>>(RR, m->V, m->vadj_ptr, m->vadj, gfix, gface, P.fflag, gverts, gcol)));
-    MR_CHECK_LAUNCH("k_rt_vgrad_b");
-    return MR_OK;
-  }
-  if (vcol) MR_TIMED(KID_RT_VGRAD_A, st, (k_rt_vgrad_a<27><<<(unsigned)(N + vbw), MR_VGRAD_NT, 0, st>>>(RR, m->V, m->vadj_ptr, m->vadj, gfix, gface, P.fflag, vraw, gnu)));
-  else MR_TIMED(KID_RT_VGRAD_A, st, (k_rt_vgrad_a<18><<<(unsigned)(N + vbw), MR_VGRAD_NT, 0, st>>>(RR, m->V, m->vadj_ptr, m->vadj, gfix, gface, P.fflag, vraw, gnu)));
-  MR_CHECK_LAUNCH("k_rt_vgrad_a");
-  if (vcol) {
-    MR_TIMED(KID_VGRAD_B, st, (k_vgrad_b<27><<<vb, 256, 0, st>>>(m->V, m->verts, m->faces, m->vadj_ptr, m->vadj, gfix, gface, P.fflag, gnu, use_n, gverts, gcol)));
-  } else {
-    MR_TIMED(KID_VGRAD_B, st, (k_vgrad_b<18><<<vb, 256, 0, st>>>(m->V, m->verts, m->faces, m->vadj_ptr, m->vadj, gfix, gface, P.fflag, gnu, use_n, gverts, gcol)));
-  }
-  MR_CHECK_LAUNCH("k_vgrad");
-  return MR_OK;
+  A.RR.bands = view_binning(g, N, NF) ? bin_bands(N, g) : 1;
+  A.RR.gviews = gviews; A.RR.gRcv = gRcv; A.RR.gtcv = gtcv;
+  A.m = m; A.gfix = w.gfix; A.gface = w.gflt; A.fflag = P.fflag;
+  A.vraw = sp->light_kind == 0 ? vraw : nullptr;
+  A.gnu = gnu; A.gverts = gverts; A.gcol = gcol;
+  A.timed = true;
+  return vcol ? launch_vertex_grads<27>(A, st) : launch_vertex_grads<18>(A, st);
+}
+
+int32_t mr_render_backward(const mr_mesh_t* m, const float* vraw, const mr_view_t* views, int64_t N, const float* cc,
+                           int64_t ncc, const mr_raster_settings_t* s, const mr_shade_params_t* sp,
+                           const float* gD, const float* gS, const float* gRGB, const void* fws, void* bws,
+                           size_t bws_bytes, float* gverts, float* gviews, float* gcol, void* stream) {
+  if (!gviews) return set_err(MR_EINVAL, "NULL argument");
+  return render_backward(m, vraw, views, N, cc, ncc, s, sp, gD, gS, gRGB, fws, bws, bws_bytes, gverts, gviews,
+                         nullptr, nullptr, gcol, stream);
+}
+
+int32_t mr_render_backward_opencv(const mr_mesh_t* m, const float* vraw, const mr_view_t* views, int64_t N,
+                                  const float* cc, int64_t ncc, const mr_raster_settings_t* s,
+                                  const mr_shade_params_t* sp, const float* gD, const float* gS, const float* gRGB,
+                                  const void* fws, void* bws, size_t bws_bytes, float* gverts, float* grad_R_cv,
+                                  float* grad_t_cv, float* gcol, void* stream) {
+  if (!grad_R_cv || !grad_t_cv) return set_err(MR_EINVAL, "NULL argument");
+  return render_backward(m, vraw, views, N, cc, ncc, s, sp, gD, gS, gRGB, fws, bws, bws_bytes, gverts, nullptr,
+                         grad_R_cv, grad_t_cv, gcol, stream);
 }
 
 // ---------------- K-deep soft shading over stored fragments ----------------
@@ -1196,22 +1115,15 @@ int32_t mr_shade_fragments_backward(const mr_mesh_t* m, const float* vraw, const
   if (vcol) MR_TIMED(KID_FRAG_SHADE_BWD, st, (k_frag_shade_bwd<27><<<grid, 256, 0, st>>>(P)));
   else MR_TIMED(KID_FRAG_SHADE_BWD, st, (k_frag_shade_bwd<18><<<grid, 256, 0, st>>>(P)));
   MR_CHECK_LAUNCH("k_frag_shade_bwd");
-  // vertex gradients of the attribute rows (interpolated positions and normals, vertex colours)
-  const int use_n = sp->light_kind == 0 && !P.sil;
-  const int vb = ceil_div(m->V * MR_VL, 256);
-  if (use_n) {
-    RtReduce R0;
-    memset(&R0, 0, sizeof(R0));
-    R0.bands = 1;
-    const int vbw = ceil_div(m->V * MR_VL, MR_VGRAD_NT);
-    if (vcol) k_rt_vgrad_a<27><<<(unsigned)vbw, MR_VGRAD_NT, 0, st>>>(R0, m->V, m->vadj_ptr, m->vadj, nullptr, gface, nullptr, vraw, gnu);
-    else k_rt_vgrad_a<18><<<(unsigned)vbw, MR_VGRAD_NT, 0, st>>>(R0, m->V, m->vadj_ptr, m->vadj, nullptr, gface, nullptr, vraw, gnu);
-    MR_CHECK_LAUNCH("k_rt_vgrad_a");
-  }
-  if (vcol) k_vgrad_b<27><<<vb, 256, 0, st>>>(m->V, m->verts, m->faces, m->vadj_ptr, m->vadj, nullptr, gface, nullptr, gnu, use_n, g_verts, g_vcolors);
-  else k_vgrad_b<18><<<vb, 256, 0, st>>>(m->V, m->verts, m->faces, m->vadj_ptr, m->vadj, nullptr, gface, nullptr, gnu, use_n, g_verts, g_vcolors);
-  MR_CHECK_LAUNCH("k_vgrad_b");
-  return MR_OK;
+  // vertex gradients of the attribute rows (interpolated positions and normals, vertex colours): float rows
+  // only, no views to reduce, not timed
+  VertexGradArgs A;
+  memset(&A, 0, sizeof(A));
+  A.RR.bands = 1;
+  A.m = m; A.gface = gface;
+  A.vraw = (sp->light_kind == 0 && !P.sil) ? vraw : nullptr;
+  A.gnu = gnu; A.gverts = g_verts; A.gcol = g_vcolors;
+  return vcol ? launch_vertex_grads<27>(A, st) : launch_vertex_grads<18>(A, st);
 }
 
 // Covered pixels of a forward (stats only; a same-address counter in the raster serialises).
@@ -1230,7 +1142,7 @@ int32_t mr_workspace_stats(const void* ws, int64_t N, int64_t Ftot, int32_t H, i
   if (!ws || !out || N <= 0 || N > 65535) return set_err(MR_EINVAL, "bad arguments");
   hipStream_t st = (hipStream_t)stream;
   BinGeom g = bin_geom(H, W, N, Ftot > 0 ? Ftot : 1, mfpb);
-  RasterWS w = carve_raster_ws((void*)ws, N, Ftot > 0 ? Ftot : 1, H, W, g);
+  RasterWS w = carve_raster_ws((void*)ws, N, Ftot > 0 ? Ftot : 1, g);
   const size_t n = (size_t)N + CTR_COUNT + (size_t)N * g.T;  // ctr, cnt and vtot are contiguous
   if (hipMemsetAsync(w.ctr + CTR_COVERED, 0, sizeof(int), st) != hipSuccess) return set_err(MR_ELAUNCH, "memset failed");
   k_count_covered<<<1024, 256, 0, st>>>(w.sface, w.ctr, w.ctr + CTR_COVERED);
@@ -1261,7 +1173,7 @@ int32_t mr_workspace_counters(const void* ws, int64_t N, int64_t Ftot, int32_t H
   if (!ws || !out8 || N <= 0 || N > 65535) return set_err(MR_EINVAL, "bad arguments");
   hipStream_t st = (hipStream_t)stream;
   BinGeom g = bin_geom(H, W, N, Ftot > 0 ? Ftot : 1, mfpb);
-  RasterWS w = carve_raster_ws((void*)ws, N, Ftot > 0 ? Ftot : 1, H, W, g);
+  RasterWS w = carve_raster_ws((void*)ws, N, Ftot > 0 ? Ftot : 1, g);
   if (hipMemcpyAsync(out8, w.ctr, sizeof(int) * CTR_COUNT, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess)
     return set_err(MR_ELAUNCH, "counter copy failed");

@@ -179,9 +179,7 @@ struct RasterWS {
   int nbcnt;       // N * bands (0: no lists)
   size_t bytes;
 };
-static RasterWS carve_raster_ws(void* base, int64_t N, int64_t Ftot, int H, int W, const BinGeom& g,
-                                int64_t Fshade = 0) {
-  (void)H; (void)W;
+static RasterWS carve_raster_ws(void* base, int64_t N, int64_t Ftot, const BinGeom& g, int64_t Fshade = 0) {
   RasterWS w;
   size_t off = 0;
   char* b = (char*)base;

@@ -1155,6 +1155,12 @@ __global__ void __launch_bounds__(1024) k_unit_order(const int4* __restrict__ un
   }
 }
 
+// Workgroups of a covered-pixel launch over at most slots_cap slots, of `resident` resident ones.
+static int shade_grid(int64_t slots_cap, int resident) {
+  const int sg = (int)(slots_cap / 4 + 1 < resident ? slots_cap / 4 + 1 : resident);
+  return (sg + 7) / 8 * 8;  // XCD-partitioned slot ranges
+}
+
 #ifndef MR_SHADE_RENDER
 #define MR_SHADE_RENDER 1
 #endif
@@ -1167,9 +1173,7 @@ static int launch_shade_render(const FwdParams& P, int64_t slots_cap, hipStream_
   if (!g1) g1 = resident_grid(k_shade_render<CH, 1>, 256, 4);
   const bool spec = CH == 3 && P.S.tex_kind == 2 && P.S.tex8 && P.S.light_kind == 0 && !P.S.zbuf_mode &&
                     !P.p2f32 && P.out_flags == (MR_OUT_DEPTH | MR_OUT_SIL | MR_OUT_RGB);
-  const int gr = spec ? g1 : g0;
-  int sg = (int)(slots_cap / 4 + 1 < gr ? slots_cap / 4 + 1 : gr);
-  sg = (sg + 7) / 8 * 8;  // XCD-partitioned slot ranges
+  const int sg = shade_grid(slots_cap, spec ? g1 : g0);
   if (spec) MR_TIMED(KID_SHADE_RENDER, st, (k_shade_render<CH, 1><<<sg, 256, 0, st>>>(P)));
   else MR_TIMED(KID_SHADE_RENDER, st, (k_shade_render<CH, 0><<<sg, 256, 0, st>>>(P)));
   MR_CHECK_LAUNCH("k_shade_render");
@@ -1199,9 +1203,20 @@ static int launch_raster_and_shade(FwdParams P, const BinGeom& g, int64_t N, hip
   if (MODE == 0 && P.emit_frag) return MR_OK;  // the raster wrote the listed tiles' fragments
   const int64_t slots_cap = N * (int64_t)g.T;
   if (MODE == 1 && MR_SHADE_RENDER) return launch_shade_render<CH>(P, slots_cap, st);
-  int sg = (int)(slots_cap / 4 + 1 < sgrid ? slots_cap / 4 + 1 : sgrid);
-  sg = (sg + 7) / 8 * 8;  // XCD-partitioned slot ranges
-  MR_TIMED(MODE == 0 ? KID_SHADE_FRAG : KID_SHADE_RENDER, st, (k_shade<MODE, CH><<<sg, 256, 0, st>>>(P)));
+  MR_TIMED(MODE == 0 ? KID_SHADE_FRAG : KID_SHADE_RENDER, st, (k_shade<MODE, CH><<<shade_grid(slots_cap, sgrid), 256, 0, st>>>(P)));
+  MR_CHECK_LAUNCH("k_shade");
+  return MR_OK;
+}
+
+// A reshade (mr_render_reshade) over a forward's stored winners: every pixel's background, then the covered pixels.
+template <int CH>
+static int launch_fill_and_shade(const FwdParams& P, int64_t slots_cap, hipStream_t st) {
+  static int fgrid = 0, sgrid = 0;
+  if (!fgrid) fgrid = resident_grid(k_fill<1, CH>, 256, 8);
+  if (!sgrid) sgrid = resident_grid(k_shade<1, CH>, 256, 6);
+  MR_TIMED(KID_FILL_FRAG, st, (k_fill<1, CH><<<fgrid, 256, 0, st>>>(P)));
+  MR_CHECK_LAUNCH("k_fill");
+  MR_TIMED(KID_SHADE_RENDER, st, (k_shade<1, CH><<<shade_grid(slots_cap, sgrid), 256, 0, st>>>(P)));
   MR_CHECK_LAUNCH("k_shade");
   return MR_OK;
 }

@@ -195,6 +195,43 @@ __global__ void __launch_bounds__(MR_VGRAD_NT) k_rt_vgrad_b(RtReduce R, int64_t 
                           xcd_block((int64_t)blockIdx.x - R.N, (int64_t)gridDim.x - R.N));
 }
 
+// The vertex gradients of per-face total rows (ACC columns), with the R/T reduction of RR's RR.N views (0: none) in
+// the first launch's leading rows. vraw (the shading read vertex normals): k_rt_vgrad_a, then k_vgrad_b with the
+// normal chain. Else k_rt_vgrad_b alone when there are views to reduce, k_vgrad_b alone when not.
+struct VertexGradArgs {
+  RtReduce RR;
+  const mr_mesh_t* m;
+  const unsigned long long* gfix;  // NULL (with fflag): float rows only
+  const float* gface;
+  const int* fflag;
+  const float* vraw;  // NULL: no normal chain
+  float* gnu;
+  float *gverts, *gcol;
+  bool timed;  // MR_TIMED under KID_RT_VGRAD_A / _B, KID_VGRAD_B
+};
+template <int ACC>
+static int launch_vertex_grads(const VertexGradArgs& A, hipStream_t st) {
+  const mr_mesh_t* m = A.m;
+  const unsigned rows = (unsigned)(A.RR.N + ceil_div(m->V * MR_VL, MR_VGRAD_NT));  // views + vertex-gather workgroups
+  int ti = A.timed ? timing_begin(st) : -1;
+  if (!A.vraw && A.RR.N > 0) {
+    k_rt_vgrad_b<ACC><<<rows, MR_VGRAD_NT, 0, st>>>(A.RR, m->V, m->vadj_ptr, m->vadj, A.gfix, A.gface, A.fflag, A.gverts, A.gcol);
+    timing_end(ti, KID_RT_VGRAD_B, st);
+    MR_CHECK_LAUNCH("k_rt_vgrad_b");
+    return MR_OK;
+  }
+  if (A.vraw) {
+    k_rt_vgrad_a<ACC><<<rows, MR_VGRAD_NT, 0, st>>>(A.RR, m->V, m->vadj_ptr, m->vadj, A.gfix, A.gface, A.fflag, A.vraw, A.gnu);
+    timing_end(ti, KID_RT_VGRAD_A, st);
+    MR_CHECK_LAUNCH("k_rt_vgrad_a");
+    ti = A.timed ? timing_begin(st) : -1;
+  }
+  k_vgrad_b<ACC><<<ceil_div(m->V * MR_VL, 256), 256, 0, st>>>(m->V, m->verts, m->faces, m->vadj_ptr, m->vadj, A.gfix, A.gface, A.fflag, A.gnu, A.vraw ? 1 : 0, A.gverts, A.gcol);
+  timing_end(ti, KID_VGRAD_B, st);
+  MR_CHECK_LAUNCH("k_vgrad_b");
+  return MR_OK;
+}
+
 // projection: face_verts[n*F+f][c] = ndc(view n, X); distinct meshes (ff = first union face of
 // each view, N+1): face_verts[f] for the faces f of view n's mesh
 __global__ void __launch_bounds__(256) k_project_faces(const float* __restrict__ verts, const int32_t* __restrict__ faces,

@@ -59,11 +59,6 @@ def mesh_topology(faces: torch.Tensor, V: int):
     return f32, vptr, vadj
 
 
-def vertex_adjacency(faces: torch.Tensor, V: int):
-    """CSR vertex -> (face << 2 | corner) adjacency (see mesh_topology)."""
-    return mesh_topology(faces, V)[1:]
-
-
 _PRIOR_CACHE: dict = {}
 
 
@@ -329,6 +324,22 @@ def views_from_opencv(R_cv, t_cv, intr, N):
     return views
 
 
+def _project_backward(v, f, vptr, vadj, views, gfv, vert_first=None, max_verts=0):
+    """(grad verts, grad R, grad T) of the projection from the face_verts gradient: mr_project_faces_backward, or
+    with vert_first (each view's first union vertex) mr_project_faces_meshes_backward."""
+    L = _lib.load()
+    N = views.shape[0]
+    gv = torch.empty_like(v)
+    gviews = torch.empty((N, 12), device=v.device)
+    mesh = (ptr(v), v.shape[0], ptr(f), f.shape[0], ptr(vptr), ptr(vadj))
+    tail = (ptr(views), N, ptr(gfv.float().contiguous()), ptr(gv), ptr(gviews), _lib.stream_handle(v.device))
+    if vert_first is None:
+        check(L.mr_project_faces_backward(*mesh, *tail))
+    else:
+        check(L.mr_project_faces_meshes_backward(*mesh, ptr(vert_first), max_verts, *tail))
+    return gv, gviews[:, :9].reshape(N, 3, 3), gviews[:, 9:12]
+
+
 class ProjectFaces(torch.autograd.Function):
     """MeshRasterizer.transform + verts_packed()[faces_packed] for one mesh shared by N views."""
 
@@ -349,14 +360,7 @@ class ProjectFaces(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         v, f, views, vptr, vadj = ctx.saved_tensors
-        L = _lib.load()
-        N = views.shape[0]
-        gv = torch.empty_like(v)
-        gviews = torch.empty((N, 12), device=v.device)
-        check(L.mr_project_faces_backward(ptr(v), v.shape[0], ptr(f), f.shape[0], ptr(vptr), ptr(vadj), ptr(views),
-                                          N, ptr(g.float().contiguous()), ptr(gv), ptr(gviews),
-                                          _lib.stream_handle(v.device)))
-        return gv, gviews[:, :9].reshape(N, 3, 3), gviews[:, 9:12], None, None
+        return _project_backward(v, f, vptr, vadj, views, g) + (None, None)
 
 
 class ProjectFacesMeshes(torch.autograd.Function):
@@ -382,15 +386,7 @@ class ProjectFacesMeshes(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         v, f, views, vptr, vadj, vert_first = ctx.saved_tensors
-        L = _lib.load()
-        N = views.shape[0]
-        gv = torch.empty_like(v)
-        gviews = torch.empty((N, 12), device=v.device)
-        check(L.mr_project_faces_meshes_backward(ptr(v), v.shape[0], ptr(f), f.shape[0], ptr(vptr), ptr(vadj),
-                                                 ptr(vert_first), ctx.max_verts, ptr(views), N,
-                                                 ptr(g.float().contiguous()), ptr(gv), ptr(gviews),
-                                                 _lib.stream_handle(v.device)))
-        return gv, gviews[:, :9].reshape(N, 3, 3), gviews[:, 9:12], None, None, None, None, None, None
+        return _project_backward(v, f, vptr, vadj, views, g, vert_first, ctx.max_verts) + (None,) * 6
 
 
 def _poses_struct(R, T, intr):
@@ -403,6 +399,19 @@ def _poses_struct(R, T, intr):
     return _lib.MrPoses(sp(R).value, sR, sp(T).value, sT, sp(it).value, sI), (R, T, it)
 
 
+def _world_inputs(verts, R, T, faces, intr, N, H, W, K, blur, persp, clip, cull, mfpb, z_clip):
+    """What a *World forward passes down: v float (V,3), the topology (f, vptr, vadj), mr_poses_t and the tensors it
+    points into, mr_raster_settings_t, and the views (N,16) / face_verts (N F,3,3) buffers the call writes."""
+    _require_cuda(verts, R, T, faces, intr)
+    v = verts.detach().float().contiguous()
+    f, vptr, vadj = mesh_topology(faces, v.shape[0])
+    ps, keep = _poses_struct(R, T, intr)
+    s = raster_settings_struct(H, W, K, blur, persp, clip, cull, mfpb, z_clip)
+    views = torch.empty((N, 16), device=v.device)
+    fv = torch.empty((N * f.shape[0], 3, 3), device=v.device)
+    return v, f, vptr, vadj, ps, keep, s, views, fv
+
+
 class RasterizeMeshesWorld(torch.autograd.Function):
     """MeshRasterizer.transform + _RasterizeFaceVerts for one mesh shared by N views, in one
     native call (mr_rasterize_meshes_world): the projection runs inside the binning's first launch,
@@ -412,16 +421,12 @@ class RasterizeMeshesWorld(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, verts, R, T, faces, intr, N, H, W, K, blur, persp, clip, cull, mfpb, z_clip=None):
-        _require_cuda(verts, R, T, faces, intr)
         ctx.set_materialize_grads(False)  # no zero-filled int64 grad for pix_to_face, none for unused outputs
         L = _lib.load()
-        v = verts.detach().float().contiguous()
-        f, vptr, vadj = mesh_topology(faces, v.shape[0])
-        N, Fn, dev = int(N), f.shape[0], v.device
-        ps, keep = _poses_struct(R, T, intr)
-        s = raster_settings_struct(H, W, K, blur, persp, clip, cull, mfpb, z_clip)
-        views = torch.empty((N, 16), device=dev)
-        fv = torch.empty((N * Fn, 3, 3), device=dev)
+        N = int(N)
+        v, f, vptr, vadj, ps, keep, s, views, fv = _world_inputs(verts, R, T, faces, intr, N, H, W, K, blur, persp,
+                                                                 clip, cull, mfpb, z_clip)
+        Fn, dev = f.shape[0], v.device
         p2f = torch.empty((N, H, W, K), dtype=torch.int64, device=dev)
         zbuf = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)
         bary = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev)
@@ -442,14 +447,7 @@ class RasterizeMeshesWorld(torch.autograd.Function):
         v, f, views, vptr, vadj, fv, p2f = ctx.saved_tensors
         H, W, K, persp, clip, blur, cull, z_clip = ctx.cfg
         gfv = rasterize_meshes_bwd(fv, p2f, gz, gb, gd, H, W, K, persp, clip, blur, cull, z_clip)
-        L = _lib.load()
-        N = views.shape[0]
-        gv = torch.empty_like(v)
-        gviews = torch.empty((N, 12), device=v.device)
-        check(L.mr_project_faces_backward(ptr(v), v.shape[0], ptr(f), f.shape[0], ptr(vptr), ptr(vadj), ptr(views),
-                                          N, ptr(gfv.contiguous()), ptr(gv), ptr(gviews),
-                                          _lib.stream_handle(v.device)))
-        return (gv, gviews[:, :9].reshape(N, 3, 3), gviews[:, 9:12]) + (None,) * 12
+        return _project_backward(v, f, vptr, vadj, views, gfv) + (None,) * 12
 
 
 class SoftSilhouetteWorld(torch.autograd.Function):
@@ -462,15 +460,11 @@ class SoftSilhouetteWorld(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, verts, R, T, faces, intr, N, H, W, K, blur, persp, clip, cull, mfpb, z_clip, sigma):
-        _require_cuda(verts, R, T, faces, intr)
         L = _lib.load()
-        v = verts.detach().float().contiguous()
-        f, vptr, vadj = mesh_topology(faces, v.shape[0])
-        N, Fn, dev = int(N), f.shape[0], v.device
-        ps, keep = _poses_struct(R, T, intr)
-        s = raster_settings_struct(H, W, K, blur, persp, clip, cull, mfpb, z_clip)
-        views = torch.empty((N, 16), device=dev)
-        fv = torch.empty((N * Fn, 3, 3), device=dev)
+        N = int(N)
+        v, f, vptr, vadj, ps, keep, s, views, fv = _world_inputs(verts, R, T, faces, intr, N, H, W, K, blur, persp,
+                                                                 clip, cull, mfpb, z_clip)
+        Fn, dev = f.shape[0], v.device
         rgba = torch.tensor([1.0, 1.0, 1.0, 0.0], device=dev).expand(N, H, W, 4).contiguous()  # background
         wsb = L.mr_soft_silhouette_workspace(N, Fn, H, W, K, s.max_faces_per_bin)
         ws = torch.empty(int(wsb), dtype=torch.uint8, device=dev)
@@ -493,11 +487,7 @@ class SoftSilhouetteWorld(torch.autograd.Function):
         gfv = torch.empty_like(fv)
         check(L.mr_soft_silhouette_backward(ptr(fv), N, f.shape[0], ctypes.byref(s), sigma,
                                             ptr(g.float().contiguous()), ptr(ws), ptr(gfv), _lib.stream_handle(dev)))
-        gv = torch.empty_like(v)
-        gviews = torch.empty((N, 12), device=dev)
-        check(L.mr_project_faces_backward(ptr(v), v.shape[0], ptr(f), f.shape[0], ptr(vptr), ptr(vadj), ptr(views),
-                                          N, ptr(gfv), ptr(gv), ptr(gviews), _lib.stream_handle(dev)))
-        return (gv, gviews[:, :9].reshape(N, 3, 3), gviews[:, 9:12]) + (None,) * 13
+        return _project_backward(v, f, vptr, vadj, views, gfv) + (None,) * 13
 
 
 def vertex_normals(verts, faces):
@@ -518,7 +508,7 @@ def _vertex_normals(v, f, vptr, vadj):
 
 
 # --------------------------------------------------------------------------- fused render
-_STRUCT_CACHE: dict = {}  # ShadeConfig values -> its ctypes structs (per-call host work of the eager loops)
+_STRUCT_CACHE: dict = {}  # ShadeConfig values -> its ctypes structs' bytes (per-call host work of the eager loops)
 _WS_CACHE: dict = {}      # workspace-size queries by their arguments
 
 
@@ -572,22 +562,23 @@ class ShadeConfig:
         """The configuration's values (field order is the dataclass's): the struct caches' key."""
         return tuple(self.__dict__.values())
 
-    def raster_struct(self):
-        k = ("r", self.key())
-        hit = _STRUCT_CACHE.get(k)
-        if hit is None:
-            hit = _STRUCT_CACHE[k] = raster_settings_struct(self.H, self.W, 1, self.blur, self.persp, self.clip,
-                                                            self.cull, self.max_faces_per_bin, self.z_clip)
-        return MrRasterSettings.from_buffer_copy(hit)  # a copy: callers set flags on it
-
-    def shade_struct(self):
-        k = ("s", self.key())
+    def struct_bytes(self, kind, key=None):
+        """The bytes of the configuration's mr_raster_settings_t ("r") or mr_shade_params_t ("s"), cached by its
+        values (key: self.key() when the caller already has it)."""
+        k = (kind, self.key() if key is None else key)
         hit = _STRUCT_CACHE.get(k)
         if hit is None:
             if len(_STRUCT_CACHE) > 256:
                 _STRUCT_CACHE.clear()
-            hit = _STRUCT_CACHE[k] = self._shade_struct()
-        return MrShadeParams.from_buffer_copy(hit)
+            hit = _STRUCT_CACHE[k] = bytes(self._shade_struct() if kind == "s" else raster_settings_struct(
+                self.H, self.W, 1, self.blur, self.persp, self.clip, self.cull, self.max_faces_per_bin, self.z_clip))
+        return hit
+
+    def raster_struct(self):
+        return MrRasterSettings.from_buffer_copy(self.struct_bytes("r"))  # a copy: callers set flags on it
+
+    def shade_struct(self):
+        return MrShadeParams.from_buffer_copy(self.struct_bytes("s"))
 
     def _shade_struct(self):
         sp = MrShadeParams()
@@ -657,40 +648,13 @@ def _mesh_struct(v, f, vptr, vadj, vn, tex: TextureArgs, vcol, ranges=None):
 _RESHADE = {"entry": None, "enabled": True}
 
 
-_EMPTY0 = {}
-
-
-def _empty0(dev):
-    """A cached empty tensor on `dev` (the placeholder saved for absent optional inputs)."""
-    t = _EMPTY0.get(dev)
-    if t is None:
-        t = _EMPTY0[dev] = torch.empty(0, device=dev)
-    return t
-
-
 def _tsig(t):
     return (t.data_ptr(), t._version, t.shape, t.stride(), t.device, t.dtype)
-
-
-def _shade_sig(cfg):
-    return cfg.key()
 
 
 def _geom_sig(v, f, R, T, intr, cfg, pose_cv, ranges, stream):
     return (_tsig(v), _tsig(f), _tsig(R), _tsig(T), _tsig(intr), cfg.H, cfg.W, cfg.persp, cfg.blur, cfg.clip, cfg.cull,
             cfg.max_faces_per_bin, cfg.z_clip, bool(pose_cv), ranges is None, stream)
-
-
-def _blob(kind, cfg, make, ckey=None):
-    """The bytes of one of cfg's ctypes structs (cached by the configuration's values; ckey: cfg.key()
-    when the caller already has it)."""
-    k = (kind, cfg.key() if ckey is None else ckey)
-    hit = _STRUCT_CACHE.get(k)
-    if hit is None:
-        if len(_STRUCT_CACHE) > 256:
-            _STRUCT_CACHE.clear()
-        hit = _STRUCT_CACHE[k] = bytes(make())
-    return hit
 
 
 def render_views(verts, R, T, faces, intr, cam_centers, cfg: ShadeConfig, tex: TextureArgs | None = None,
@@ -713,9 +677,9 @@ def render_views(verts, R, T, faces, intr, cam_centers, cfg: ShadeConfig, tex: T
         cfg = ShadeConfig(**{**cfg.__dict__, "light_kind": 1})
     dev = verts.device
     f, vptr, vadj = mesh_topology(faces, verts.shape[0])
-    ssig = cfg.key()  # the shading signature (_shade_sig) and the struct caches' key
-    rsb = _blob("rb", cfg, cfg.raster_struct, ssig)
-    spb = _blob("sb", cfg, cfg.shade_struct, ssig)
+    ssig = cfg.key()  # the shading signature and the struct cache's key
+    rsb = cfg.struct_bytes("r", ssig)
+    spb = cfg.struct_bytes("s", ssig)
     stream = _lib.stream_handle(dev).value
     geom = _geom_sig(verts, f, R, T, intr, cfg, pose_cv, ranges, stream)
     ent = _RESHADE["entry"]
@@ -778,6 +742,19 @@ def _padded_rgba(tex_map):
     return rgba
 
 
+def _frag_shade_struct(cfg):
+    """cfg's mr_shade_params_t as mr_shade_fragments_forward / _backward take it: exactly one of the silhouette
+    (not cfg.want_rgb) and RGB outputs, RGBA pixels."""
+    sil = not cfg.want_rgb
+    sp = cfg.shade_struct()
+    sp.out_flags = _lib.MR_OUT_SIL if sil else (_lib.MR_OUT_RGB | (_lib.MR_OUT_HARD if cfg.hard else 0))
+    sp.out_flags |= _lib.MR_FRAG_SORTED if cfg.frag_sorted else 0
+    sp.rgb_channels = 4
+    if sil:
+        sp.light_kind = 1  # the silhouette blend reads no lighting (no vertex normals needed)
+    return sp
+
+
 class ShadeFragments(torch.autograd.Function):
     """SoftPhongShader / SoftSilhouetteShader over stored Fragments of ONE mesh shared by the N
     views (pix_to_face = n*F + f), any faces_per_pixel: mr_shade_fragments_forward / _backward
@@ -810,12 +787,7 @@ class ShadeFragments(torch.autograd.Function):
             tex = TextureArgs(2, verts_uvs.detach().float().contiguous(), faces_uvs.to(torch.int32).contiguous(),
                               _padded_rgba(tex_map))
         mesh = _mesh_struct(v, f, vptr, vadj, vn, tex, vcol, ranges)
-        sp = cfg.shade_struct()
-        sp.out_flags = _lib.MR_OUT_SIL if sil else (_lib.MR_OUT_RGB | (_lib.MR_OUT_HARD if cfg.hard else 0))
-        sp.out_flags |= _lib.MR_FRAG_SORTED if cfg.frag_sorted else 0
-        sp.rgb_channels = 4
-        if sil:
-            sp.light_kind = 1  # the silhouette blend reads no lighting (no vertex normals needed)
+        sp = _frag_shade_struct(cfg)
         cc = cam_centers.float().contiguous().reshape(-1, 3)
         frag = [t.contiguous() for t in (p2f, zbuf.detach().float(), bary.detach().float(), dists.detach().float())]
         wsb = L.mr_shade_fragments_workspace(f.shape[0])
@@ -843,12 +815,7 @@ class ShadeFragments(torch.autograd.Function):
         e = lambda t: t if t.numel() else None  # noqa: E731
         tex = TextureArgs(ctx.tex_kind, e(vuv), e(fuv), e(rgba_map))
         mesh = _mesh_struct(v, f, vptr, vadj, e(vn), tex, e(vcol), ctx.ranges)
-        sp = cfg.shade_struct()
-        sp.out_flags = (_lib.MR_OUT_RGB | (_lib.MR_OUT_HARD if cfg.hard else 0)) if cfg.want_rgb else _lib.MR_OUT_SIL
-        sp.out_flags |= _lib.MR_FRAG_SORTED if cfg.frag_sorted else 0
-        sp.rgb_channels = 4
-        if not cfg.want_rgb:
-            sp.light_kind = 1
+        sp = _frag_shade_struct(cfg)
         bwb = L.mr_shade_fragments_backward_workspace(v.shape[0], f.shape[0])
         bws = torch.empty(int(bwb), dtype=torch.uint8, device=dev)
         # gradients that are zero by construction stay None (NULL): the silhouette blend reads only the
