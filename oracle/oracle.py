@@ -528,18 +528,20 @@ DEFAULT_MAT = {"ambient": (1.0, 1.0, 1.0), "diffuse": (1.0, 1.0, 1.0), "specular
 def render_ref(verts, faces, R, T, intr, H, W, *, texture=None, light=DEFAULT_LIGHT, mat=DEFAULT_MAT,
                cam_center=(0.0, 0.0, 0.0), sigma=1e-4, gamma=1e-4, bg=(1.0, 1.0, 1.0), sigma_sil=1e-4,
                znear=1.0, zfar=100.0, persp=True, K=1, blur=0.0, clip=False, z_clip=None, window=None,
-               precision="f32"):
+               precision="f32", cull=False):
     """The reference CPU render path for one mesh shared by N views:
     depth = relu(zbuf[...,0]); sil = sigmoid_alpha_blend alpha; rgba = softmax_rgb_blend(phong).
     texture: None (white), ("vertex", vcolors (V,3)), ("uv", verts_uvs, faces_uvs, map (Ht,Wt,C)).
     precision="f64": the float64 shadow (same decisions, every value and gradient in float64; see
     frag_eval_t), which measures the f32 oracle's own rounding error.
+    cull: RasterizationSettings.cull_backfaces, passed to every rasterizer call (the near-plane split
+    keeps a face's winding, so its sub-triangles are culled with it).
     Returns dict with depth, sil, rgba, fragments."""
     N = R.shape[0]
     Fn = faces.shape[0]
     if precision == "f64":
         p2f, zbuf, bary, dists, fv = _shadow_fragments(verts, faces, R, T, intr, H, W, K, blur, persp, clip, z_clip,
-                                                       window)
+                                                       window, cull)
         verts = verts.double()
         if texture is not None:
             texture = tuple(t.double() if torch.is_tensor(t) and t.is_floating_point() else t for t in texture)
@@ -549,12 +551,12 @@ def render_ref(verts, faces, R, T, intr, H, W, *, texture=None, light=DEFAULT_LI
         first = torch.arange(N, dtype=torch.int64) * Fn
         count = torch.full((N,), Fn, dtype=torch.int64)
         if z_clip is None:
-            p2f, zbuf, bary, dists = RasterizeRef.apply(fv, first, count, H, W, K, blur, persp, clip, False, None,
+            p2f, zbuf, bary, dists = RasterizeRef.apply(fv, first, count, H, W, K, blur, persp, clip, cull, None,
                                                         window)
         else:  # MeshRasterizer with a znear camera: clip_faces -> raster -> convert back (upstream clip.py)
             cf = clip_faces_ref(fv, first, count, z_clip, persp)
             p2f_c, zbuf, bary_c, dists = RasterizeRef.apply(cf["face_verts"], cf["first"], cf["count"], H, W, K,
-                                                            blur, persp, clip, False, cf["neighbor"], window)
+                                                            blur, persp, clip, cull, cf["neighbor"], window)
             p2f, bary = unclip_fragments(p2f_c, bary_c, cf)
         zbuf, bary, dists = _jitter(zbuf), _jitter(bary), _jitter(dists)  # conditioning probe (if active)
     local = p2f.clone()
@@ -695,7 +697,7 @@ def frag_eval_t(face_verts, p2f, H, W, persp=True, clip=False):
     return zbuf, bary, dists
 
 
-def _shadow_fragments(verts, faces, R, T, intr, H, W, K, blur, persp, clip, z_clip, window):
+def _shadow_fragments(verts, faces, R, T, intr, H, W, K, blur, persp, clip, z_clip, window, cull=False):
     """f32 decisions (projection + near-plane split + C raster), then the float64 differentiable
     re-evaluation of the kept fragments. Returns (p2f, zbuf, bary, dists, face_verts64)."""
     N = R.shape[0]
@@ -707,10 +709,10 @@ def _shadow_fragments(verts, faces, R, T, intr, H, W, K, blur, persp, clip, z_cl
                                    intr.detach().float())
         if z_clip is not None:
             cf32 = clip_faces_ref(fv32, first, count, z_clip, persp)
-            p2f_c = raster_fwd(cf32["face_verts"], cf32["first"], cf32["count"], H, W, K, blur, persp, clip, False,
+            p2f_c = raster_fwd(cf32["face_verts"], cf32["first"], cf32["count"], H, W, K, blur, persp, clip, cull,
                                cf32["neighbor"], window)[0]
         else:
-            p2f_c = raster_fwd(fv32, first, count, H, W, K, blur, persp, clip, False, None, window)[0]
+            p2f_c = raster_fwd(fv32, first, count, H, W, K, blur, persp, clip, cull, None, window)[0]
     fv = project_faces_torch(verts.double(), faces, R.double(), T.double(), intr.double())
     if z_clip is None:
         zbuf, bary, dists = frag_eval_t(fv, p2f_c, H, W, persp, clip)

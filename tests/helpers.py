@@ -1,4 +1,5 @@
 """Shared test scaffolding: canonical camera batches for any asset."""
+import functools
 import math
 
 import numpy as np
@@ -11,6 +12,43 @@ from torch_renderer_amd.transforms import opencv_look_at, opencv_to_pytorch3d
 def mesh_arrays(name):
     d = load_asset_arrays(name)
     return torch.from_numpy(d["verts"]).float(), torch.from_numpy(d["faces"]).long(), d
+
+
+@functools.lru_cache(maxsize=None)
+def _jittered_ico(level):
+    from torch_renderer_amd.utils import ico_sphere
+
+    m = ico_sphere(level)
+    v = m.verts_list()[0].float()
+    # the deterministic jitter of tests/test_gpu_mesh_priors._jitter: 0.05 * randn, seed 0
+    v = v + 0.05 * torch.randn(v.shape, generator=torch.Generator().manual_seed(0))
+    return v, m.faces_list()[0].long()
+
+
+def jittered_ico(level, flip=False):
+    """(verts, faces) of the jittered ico-sphere (level 0: 12 / 20, 1: 42 / 80, 2: 162 / 320): a closed,
+    well-conditioned mesh with one front and one back layer per pixel, so that back-face culling
+    halves the K-deep fragments. flip=True reverses every face's winding (the outside becomes the
+    back face: culling then shows the far inside instead of the near outside). Fresh copies."""
+    v, f = _jittered_ico(level)
+    return v.clone(), (f[:, [0, 2, 1]] if flip else f).clone()
+
+
+def assert_cap(name, ref, spread, tol=1e-4, share=True):
+    """The condition that keeps report()'s conditioning allowance from emptying a check, asserted
+    from the oracle runs alone (oracle_runs' ref and spread) before any GPU output is looked at:
+    report relaxes an entry whose spread exceeds a tenth of its bar to bar + 10 * spread, so the
+    input must keep max(spread / bar) <= 10 and (share: images and vertex gradients) at most a
+    third of the entries ill-conditioned. An input that breaks this is replaced, not the cap."""
+    ref = ref.detach().float().cpu()
+    spread = spread.detach().float().cpu()
+    bar = tol * ref.abs().clamp(min=1.0)
+    worst = (spread / bar).max().item() if ref.numel() else 0.0
+    n_ill = int((spread > 0.1 * bar).sum())
+    print(f"[cap] {name}: max spread / bar = {worst:.2f}, ill-conditioned = {n_ill} / {ref.numel()}")
+    assert worst <= 10.0, f"{name}: the f32 oracle's spread is {worst:.1f} x the bar (cap 10)"
+    if share:
+        assert 3 * n_ill <= ref.numel(), f"{name}: {n_ill} of {ref.numel()} entries ill-conditioned (cap 1/3)"
 
 
 def canonical_views(verts, N, H, W, dist=None, fov_deg=60.0, seed=0, elev_range=(-20.0, 60.0)):

@@ -202,6 +202,43 @@ def test_golden_fixtures_reproduce(fname):
     assert np.array_equal(dists.numpy().view(np.int32), d["dists"].view(np.int32))
 
 
+@pytest.mark.parametrize("K,blur,clip,flip", [(1, 0.0, False, False), (4, 2e-4, True, False), (1, 0.0, False, True)])
+def test_cull_backfaces_equals_rasterizing_the_front_faces_only(K, blur, clip, flip):
+    """cull=True validated without using it: per view, drop the faces whose signed NDC area
+    edge_fn(v0, v1, v2) is negative from the packed list (first / count rebuilt), rasterize the rest
+    with cull=False and map the ids back. pix_to_face equal; zbuf, bary and dists bitwise. On the
+    closed sphere at K = 1 culling changes nothing (the nearest face is a front face); with the winding
+    flipped it changes every covered pixel."""
+    from tests.helpers import jittered_ico
+
+    H, W, N = 40, 56, 2
+    verts, faces = jittered_ico(2, flip)
+    R, T, intr, _ = canonical_views(verts, N, H, W)
+    fv = O.project_faces_torch(verts, faces, R, T, intr)
+    Fn = faces.shape[0]
+    first, count = torch.arange(N) * Fn, torch.full((N,), Fn)
+    culled = O.raster_fwd(fv, first, count, H, W, K, blur, True, clip, True)
+    x, y = fv[:, :, 0], fv[:, :, 1]
+    area = (x[:, 0] - x[:, 1]) * (y[:, 2] - y[:, 1]) - (y[:, 0] - y[:, 1]) * (x[:, 2] - x[:, 1])  # edge_fn(v0, v1, v2)
+    keep = ~(area < 0)
+    assert 0.3 * N * Fn < int(keep.sum()) < 0.7 * N * Fn  # a closed mesh: about half of the faces face the camera
+    ids = keep.nonzero()[:, 0]
+    cnt = keep.view(N, Fn).sum(1)
+    front = O.raster_fwd(fv[ids].contiguous(), torch.cumsum(cnt, 0) - cnt, cnt, H, W, K, blur, True, clip, False)
+    p2f = torch.where(front[0] >= 0, ids[front[0].clamp(min=0)], front[0])
+    assert (culled[0] >= 0).sum() > 200
+    both = O.raster_fwd(fv, first, count, H, W, K, blur, True, clip, False)
+    if K > 1:  # the back layer is gone
+        assert (culled[0] >= 0).sum() < 0.75 * (both[0] >= 0).sum()
+    elif flip:  # the far inside instead of the near outside
+        assert (culled[0] != both[0])[both[0] >= 0].all()
+    else:
+        assert torch.equal(culled[0], both[0])
+    assert torch.equal(culled[0], p2f)
+    for a, b, nm in zip(culled[1:], front[1:], ("zbuf", "bary", "dists")):
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32)), f"{nm} not bitwise"
+
+
 def test_oracle_under_address_and_ub_sanitizers():
     """the C restatement built with -fsanitize=address,undefined and driven through
     every entry point (forward, neighbour rule, pair mode, window, K > 1, blur, backward,
