@@ -22,6 +22,8 @@ def main():
     ap.add_argument("--mesh", default="cow")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--dist", type=float, default=0.5)
+    ap.add_argument("--only", choices=("fragments", "render"), default=None,
+                    help="time the fragment pass or the fused render alone (default: both in every iteration)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     m = load_asset(a.mesh, device=dev)
@@ -44,14 +46,17 @@ def main():
     gC = torch.rand(a.views, H, W, 3, device=dev)
 
     def run():
-        Kn.rasterize_meshes_fwd(fv, first, count, H, W)
+        if a.only != "render":
+            Kn.rasterize_meshes_fwd(fv, first, count, H, W)
+        if a.only == "fragments":
+            return None
         out = Kn.render_views(vg, R, T, f, intr, torch.zeros(1, 3, device=dev), cfg, tex)
         torch.autograd.backward([out["depth"], out["sil"], out["rgb"]], [gD, gS, gC])
         return out
 
     out = run()
     torch.cuda.synchronize()
-    cov = (out["pix_to_face32"] >= 0).float().mean().item()
+    cov = (out["pix_to_face32"] >= 0).float().mean().item() if out is not None else float("nan")
     _lib.timing_enable(True)
     for _ in range(a.iters):
         run()

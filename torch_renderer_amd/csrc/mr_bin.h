@@ -152,10 +152,6 @@ MR_DEV bool rec_tiles(const SetupParams& P, const FaceRec& r, int& tx0, int& tx1
   return true;
 }
 
-MR_DEV FaceRec make_rec_core(int cull, int persp, uint32_t face, const float v[3][3]);
-MR_DEV FaceRec make_rec(const SetupParams& P, uint32_t face, const float v[3][3]) {
-  return make_rec_core(P.cull, P.persp, face, v);
-}
 MR_DEV FaceRec make_rec_core(int cull, int persp, uint32_t face, const float v[3][3]) {
   FaceRec r;
   r.x0 = v[0][0]; r.y0 = v[0][1]; r.z0 = v[0][2];
@@ -178,6 +174,9 @@ MR_DEV FaceRec make_rec_core(int cull, int persp, uint32_t face, const float v[3
   if (persp) fast = fast && r.z0 > 0.0f && r.z1 > 0.0f && r.z2 > 0.0f;
   r.flags = (valid ? FR_VALID : 0u) | (fast ? FR_FAST : 0u);
   return r;
+}
+MR_DEV FaceRec make_rec(const SetupParams& P, uint32_t face, const float v[3][3]) {
+  return make_rec_core(P.cull, P.persp, face, v);
 }
 
 MR_DEV void world_face_verts(const float* __restrict__ verts, const int32_t* __restrict__ faces, int64_t f,
@@ -221,34 +220,118 @@ MR_DEV FaceRec build_records(const SetupParams& P, int64_t rid, uint32_t face, c
   return r0;
 }
 
-MR_DEV int rec_tile_count(const SetupParams& P, const FaceRec& r) {
+// The tiles of record r's rectangle, row by row: fn(ty * TX + tx) for each. Returns how many (0: the
+// record is invalid or off the image).
+template <typename Fn>
+MR_DEV int rec_each_tile(const SetupParams& P, const FaceRec& r, Fn&& fn) {
   int tx0, tx1, ty0, ty1;
   if (!rec_tiles(P, r, tx0, tx1, ty0, ty1)) return 0;
-  return (tx1 - tx0 + 1) * (ty1 - ty0 + 1);
+  const int nt = (tx1 - tx0 + 1) * (ty1 - ty0 + 1);
+  for (int ty = ty0; ty <= ty1; ++ty)
+    for (int tx = tx0; tx <= tx1; ++tx) fn(ty * P.TX + tx);
+  return nt;
 }
 
-// World mode (one mesh shared by N views, rec = n*F + f): project, write the record,
-// count tile overlaps through an LDS histogram, flush one global atomic per touched tile
-// and one per wave into the view's entry total.
-template <bool LDS>
-__global__ void __launch_bounds__(256) k_bin_count_world(SetupParams P, const float* __restrict__ verts,
-                                                         const int32_t* __restrict__ faces, int64_t F,
-                                                         const ViewRec* __restrict__ views, int fpt) {
-  // fpt faces per thread: the per-block LDS histogram clear and flush (T entries each) are
-  // paid once per 256 * fpt faces
-  extern __shared__ __attribute__((aligned(16))) int hist[];
-  const int n = blockIdx.y;
-  if (LDS) {
-    for (int i = threadIdx.x; i < P.T; i += blockDim.x) hist[i] = 0;
-    __syncthreads();
-  }
-  int mine = 0;
-  const ViewRec V = views[n];
-  int64_t Fv = F, rbase = (int64_t)n * F, fbase = 0;  // as k_bin_rect_world
+// Record q of face instance rid: q = 0 the instance's own record; q = 1 the second triangle of a split
+// face (FR_PAIR), false if there is none.
+MR_DEV bool rec_q(const SetupParams& P, int64_t rid, int q, FaceRec& r) {
+  r = P.recs[rid];
+  if (q == 0) return true;
+  if (!(r.flags & FR_PAIR)) return false;
+  r = P.recs[P.NF + rid];
+  return true;
+}
+
+// World mode, view n's faces: mesh faces [fbase, fbase + Fv) -> records [rbase, rbase + Fv). One mesh
+// shared by the N views of F faces each (rec = n*F + f), or with P.vff distinct meshes: view n renders
+// mesh n (records = union faces).
+MR_DEV void view_faces(const SetupParams& P, int64_t F, int n, int64_t& Fv, int64_t& rbase, int64_t& fbase) {
+  Fv = F;
+  rbase = (int64_t)n * F;
+  fbase = 0;
   if (P.vff) {
     rbase = fbase = P.vff[n];
     Fv = P.vff[n + 1] - rbase;
   }
+}
+
+// A workgroup's LDS tile histogram (P.T ints): cleared (ends with a barrier), and flushed into view n's
+// per-tile counts with one global atomic per touched tile (the caller's barrier precedes it).
+MR_DEV void hist_clear(const SetupParams& P, int* hist) {
+  for (int i = threadIdx.x; i < P.T; i += blockDim.x) hist[i] = 0;
+  __syncthreads();
+}
+MR_DEV void hist_flush(const SetupParams& P, const int* hist, int n) {
+  for (int i = threadIdx.x; i < P.T; i += blockDim.x)
+    if (hist[i]) atomicAdd(&P.cnt[(int64_t)n * P.T + i], hist[i]);
+}
+
+// The tile overlaps of one face instance's record(s) (r and, for a split face, r2: build_records) counted
+// for view n, through the LDS histogram `hist` with lds (uniform), else with global atomics. Returns the
+// instance's entries.
+MR_DEV int count_tiles(const SetupParams& P, const FaceRec& r, const FaceRec& r2, int n, int* hist, bool lds) {
+  int m = 0;
+  for (int q = 0; q < 2; ++q)
+    m += rec_each_tile(P, q == 0 ? r : r2, [&](int t) {
+      if (lds) atomicAdd(&hist[t], 1);
+      else atomicAdd(&P.cnt[(int64_t)n * P.T + t], 1);
+    });
+  return m;
+}
+
+// The fill of one workgroup's face instances: each(fn) calls fn(rid, n) for every instance (record id,
+// view). With lds (uniform; every instance in view n0): histogram in `hist`, one block of each touched
+// tile's list reserved with one global atomic, scatter through the LDS cursors; else one global atomic
+// per (record, tile).
+template <typename Each>
+MR_DEV void bin_fill_body(const SetupParams& P, int* hist, bool lds, int n0, Each&& each) {
+  const int nq = P.clipz ? 2 : 1;
+  // fn(record, its id, view) for every record of the instances
+  auto each_rec = [&](auto&& fn) {
+    each([&](int64_t rid, int n) {
+      for (int q = 0; q < nq; ++q) {
+        FaceRec r;
+        if (rec_q(P, rid, q, r)) fn(r, (int)(rid + (q ? P.NF : 0)), n);
+      }
+    });
+  };
+  if (lds) {
+    hist_clear(P, hist);
+    each_rec([&](const FaceRec& r, int, int) { rec_each_tile(P, r, [&](int t) { atomicAdd(&hist[t], 1); }); });
+    __syncthreads();
+    const int vb = P.vbase[n0];
+    for (int i = threadIdx.x; i < P.T; i += blockDim.x)
+      if (hist[i]) hist[i] = vb + atomicAdd(&P.cur[(int64_t)n0 * P.T + i], hist[i]);  // reserve a block
+    __syncthreads();
+    each_rec([&](const FaceRec& r, int id, int) {
+      rec_each_tile(P, r, [&](int t) {
+        const int pos = atomicAdd(&hist[t], 1);
+        if (pos < P.list_cap) P.list[pos] = id;
+      });
+    });
+  } else {
+    each_rec([&](const FaceRec& r, int id, int n) {
+      rec_each_tile(P, r, [&](int t) {
+        const int pos = P.vbase[n] + atomicAdd(&P.cur[(int64_t)n * P.T + t], 1);
+        if (pos < P.list_cap) P.list[pos] = id;
+      });
+    });
+  }
+}
+
+// World mode: grid row n is view n; a thread takes fpt faces (the per-block LDS histogram clear and
+// flush, T entries each, are paid once per 256 * fpt faces). The count projects the faces.
+template <bool LDS>
+__global__ void __launch_bounds__(256) k_bin_count_world(SetupParams P, const float* __restrict__ verts,
+                                                         const int32_t* __restrict__ faces, int64_t F,
+                                                         const ViewRec* __restrict__ views, int fpt) {
+  extern __shared__ __attribute__((aligned(16))) int hist[];
+  const int n = blockIdx.y;
+  if (LDS) hist_clear(P, hist);
+  int mine = 0;
+  const ViewRec V = views[n];
+  int64_t Fv, rbase, fbase;
+  view_faces(P, F, n, Fv, rbase, fbase);
   for (int k = 0; k < fpt; ++k) {
     const int64_t f = ((int64_t)blockIdx.x * fpt + k) * blockDim.x + threadIdx.x;
     if (f >= Fv) break;
@@ -257,25 +340,10 @@ __global__ void __launch_bounds__(256) k_bin_count_world(SetupParams P, const fl
     FaceRec r2;
     const FaceRec r = build_records(P, rbase + f, (uint32_t)(fbase + f), v, r2);
     P.recs[rbase + f] = r;
-    for (int q = 0; q < 2; ++q) {
-      const FaceRec& rq = q == 0 ? r : r2;
-      int tx0, tx1, ty0, ty1;
-      if (rec_tiles(P, rq, tx0, tx1, ty0, ty1)) {
-        mine += (tx1 - tx0 + 1) * (ty1 - ty0 + 1);
-        for (int ty = ty0; ty <= ty1; ++ty)
-          for (int tx = tx0; tx <= tx1; ++tx) {
-            const int t = ty * P.TX + tx;
-            if (LDS) atomicAdd(&hist[t], 1);
-            else atomicAdd(&P.cnt[(int64_t)n * P.T + t], 1);
-          }
-      }
-    }
+    mine += count_tiles(P, r, r2, n, hist, LDS);
   }
-  block_add_256(mine, &P.vtot[n]);  // also the barrier before the histogram flush
-  if (LDS) {
-    for (int i = threadIdx.x; i < P.T; i += blockDim.x)
-      if (hist[i]) atomicAdd(&P.cnt[(int64_t)n * P.T + i], hist[i]);
-  }
+  block_add_256(mine, &P.vtot[n]);  // one atomic into the view's entry total; also the barrier before the flush
+  if (LDS) hist_flush(P, hist, n);
 }
 
 template <bool LDS>
@@ -293,70 +361,14 @@ __global__ void __launch_bounds__(256) k_bin_fill_world(SetupParams P, int64_t F
     }
     return;
   }
-  const int64_t f0 = (int64_t)blockIdx.x * fpt * blockDim.x + threadIdx.x;
-  int64_t Fv = F, rbase = (int64_t)n * F;  // view n's records [rbase, rbase + Fv), as k_bin_count_world
-  if (P.vff) {
-    rbase = P.vff[n];
-    Fv = P.vff[n + 1] - rbase;
-  }
-  // q = 0: the face instance's record; q = 1: the second triangle of a split face (FR_PAIR)
-  auto rec_q = [&](int64_t f, int q, FaceRec& r) -> bool {
-    const int64_t rid = rbase + f;
-    r = P.recs[rid];
-    if (q == 0) return true;
-    if (!(r.flags & FR_PAIR)) return false;
-    r = P.recs[P.NF + rid];
-    return true;
-  };
-  const int nq = P.clipz ? 2 : 1;
-  if (LDS) {
-    for (int i = threadIdx.x; i < P.T; i += blockDim.x) hist[i] = 0;
-    __syncthreads();
+  int64_t Fv, rbase, fbase;
+  view_faces(P, F, n, Fv, rbase, fbase);
+  bin_fill_body(P, hist, LDS, n, [&](auto&& fn) {
     for (int k = 0; k < fpt; ++k) {
-      const int64_t f = f0 + (int64_t)k * blockDim.x;
-      for (int q = 0; q < nq && f < Fv; ++q) {
-        FaceRec r;
-        int tx0, tx1, ty0, ty1;
-        if (rec_q(f, q, r) && rec_tiles(P, r, tx0, tx1, ty0, ty1))
-          for (int ty = ty0; ty <= ty1; ++ty)
-            for (int tx = tx0; tx <= tx1; ++tx) atomicAdd(&hist[ty * P.TX + tx], 1);
-      }
+      const int64_t f = ((int64_t)blockIdx.x * fpt + k) * blockDim.x + threadIdx.x;
+      if (f < Fv) fn(rbase + f, n);
     }
-    __syncthreads();
-    const int vb = P.vbase[n];
-    for (int i = threadIdx.x; i < P.T; i += blockDim.x)
-      if (hist[i]) hist[i] = vb + atomicAdd(&P.cur[(int64_t)n * P.T + i], hist[i]);  // reserve a block
-    __syncthreads();
-    for (int k = 0; k < fpt; ++k) {
-      const int64_t f = f0 + (int64_t)k * blockDim.x;
-      for (int q = 0; q < nq && f < Fv; ++q) {
-        const int rid = (int)(rbase + f + (q ? P.NF : 0));
-        FaceRec r;
-        int tx0, tx1, ty0, ty1;
-        if (rec_q(f, q, r) && rec_tiles(P, r, tx0, tx1, ty0, ty1))
-          for (int ty = ty0; ty <= ty1; ++ty)
-            for (int tx = tx0; tx <= tx1; ++tx) {
-              const int pos = atomicAdd(&hist[ty * P.TX + tx], 1);
-              if (pos < P.list_cap) P.list[pos] = rid;
-            }
-      }
-    }
-  } else {
-    for (int k = 0; k < fpt; ++k) {
-      const int64_t f = f0 + (int64_t)k * blockDim.x;
-      for (int q = 0; q < nq && f < Fv; ++q) {
-        const int rid = (int)(rbase + f + (q ? P.NF : 0));
-        FaceRec r;
-        int tx0, tx1, ty0, ty1;
-        if (rec_q(f, q, r) && rec_tiles(P, r, tx0, tx1, ty0, ty1))
-          for (int ty = ty0; ty <= ty1; ++ty)
-            for (int tx = tx0; tx <= tx1; ++tx) {
-              const int pos = P.vbase[n] + atomicAdd(&P.cur[(int64_t)n * P.T + ty * P.TX + tx], 1);
-              if (pos < P.list_cap) P.list[pos] = rid;
-            }
-      }
-    }
-  }
+  });
 }
 
 MR_DEV int mesh_of_face(const int64_t* __restrict__ first, int64_t N, int64_t f) {
@@ -392,21 +404,25 @@ MR_DEV int mesh_of_face_lds(const int* first32, int64_t N, int64_t f) {
   return lo;
 }
 
-// Workgroup prologue: cache the mesh offsets in LDS; stage this workgroup's face_verts in LDS.
+// The face_verts of a workgroup's faces [f0, f0 + nf) staged in LDS (9 floats per face): 16-B loads when
+// the run starts 16-B aligned (f0 a multiple of 4 and fv aligned), else scalar loads. No barrier.
+MR_DEV void stage_face_verts(const float* fv, int64_t f0, int nf, float* sfv) {
+  const float4* src = (const float4*)(fv + 9 * f0);
+  const int n4 = ((uintptr_t)src & 15) == 0 ? 9 * nf / 4 : 0;
+  for (int i = threadIdx.x; i < n4; i += blockDim.x) ((float4*)sfv)[i] = src[i];
+  for (int i = 4 * n4 + threadIdx.x; i < 9 * nf; i += blockDim.x) sfv[i] = fv[9 * f0 + i];
+}
+
+// Workgroup prologue: cache the mesh offsets in LDS; stage this workgroup's face_verts in LDS (sfv
+// NULL: the fill reads none).
 MR_DEV FvBlock fv_block_setup(const float* __restrict__ fv, int64_t Ftot, const int64_t* __restrict__ first, int64_t N,
-                              int* first32, float* sfv, bool stage) {
+                              int* first32, float* sfv) {
   FvBlock B;
   B.f0 = (int64_t)blockIdx.x * blockDim.x * MR_FV_FPT;
   B.nf = Ftot - B.f0 < (int64_t)blockDim.x * MR_FV_FPT ? Ftot - B.f0 : (int64_t)blockDim.x * MR_FV_FPT;
   if (N <= MR_FV_NMAX)
     for (int i = threadIdx.x; i < N; i += blockDim.x) first32[i] = (int)first[i];
-  if (stage) {
-    // 9 floats per face, the workgroup's floats start 16-B aligned (f0 is a multiple of 4)
-    const float4* src = (const float4*)(fv + 9 * B.f0);
-    const int n4 = ((uintptr_t)src & 15) == 0 ? (int)(9 * B.nf) / 4 : 0;  // else scalar loads below
-    for (int i = threadIdx.x; i < n4; i += blockDim.x) ((float4*)sfv)[i] = src[i];
-    for (int i = 4 * n4 + threadIdx.x; i < 9 * B.nf; i += blockDim.x) sfv[i] = fv[9 * B.f0 + i];
-  }
+  if (sfv) stage_face_verts(fv, B.f0, (int)B.nf, sfv);
   __syncthreads();
   B.n0 = N <= MR_FV_NMAX ? mesh_of_face_lds(first32, N, B.f0) : mesh_of_face(first, N, B.f0);
   B.n1 = N <= MR_FV_NMAX ? mesh_of_face_lds(first32, N, B.f0 + B.nf - 1) : mesh_of_face(first, N, B.f0 + B.nf - 1);
@@ -424,17 +440,15 @@ __global__ void __launch_bounds__(256) k_bin_count_fv(SetupParams P, const float
   extern __shared__ __attribute__((aligned(16))) int hist[];
   __shared__ __attribute__((aligned(16))) float sfv[9 * 256 * MR_FV_FPT];
   __shared__ int first32[MR_FV_NMAX];
-  const FvBlock B = fv_block_setup(fv, Ftot, first, N, first32, sfv, true);
+  const FvBlock B = fv_block_setup(fv, Ftot, first, N, first32, sfv);
   const bool lds = LDS && B.n0 == B.n1;  // uniform over the workgroup
-  if (lds) {
-    for (int i = threadIdx.x; i < P.T; i += blockDim.x) hist[i] = 0;
-    __syncthreads();
-  }
+  if (lds) hist_clear(P, hist);
   // entry totals: of the first mesh (mine) and, in a workgroup that straddles meshes, of the
   // last (mine1) — one block-wide sum each; only meshes strictly inside the workgroup's face run
   // (small meshes) take a per-face atomic. (Per-face atomics on the few total counters of a
   // straddling workgroup serialise at the L2: they made this kernel 10x slower.)
   int mine = 0, mine1 = 0;
+#pragma unroll 1  // (one copy of the record code)
   for (int k = 0; k < MR_FV_FPT; ++k) {
     const int64_t lf = (int64_t)k * blockDim.x + threadIdx.x;
     if (lf >= B.nf) break;
@@ -446,19 +460,7 @@ __global__ void __launch_bounds__(256) k_bin_count_fv(SetupParams P, const float
     FaceRec r2;
     const FaceRec r = build_records(P, f, (uint32_t)f, v, r2);
     P.recs[f] = r;
-    int m = 0;
-    for (int q = 0; q < 2; ++q) {
-      const FaceRec& rq = q == 0 ? r : r2;
-      int tx0, tx1, ty0, ty1;
-      if (rec_tiles(P, rq, tx0, tx1, ty0, ty1)) {
-        m += (tx1 - tx0 + 1) * (ty1 - ty0 + 1);
-        for (int ty = ty0; ty <= ty1; ++ty)
-          for (int tx = tx0; tx <= tx1; ++tx) {
-            if (lds) atomicAdd(&hist[ty * P.TX + tx], 1);
-            else atomicAdd(&P.cnt[(int64_t)n * P.T + ty * P.TX + tx], 1);
-          }
-      }
-    }
+    const int m = count_tiles(P, r, r2, n, hist, lds);
     if (n == B.n0) mine += m;
     else if (n == B.n1) mine1 += m;
     else if (m) atomicAdd(&P.vtot[n], m);
@@ -468,10 +470,7 @@ __global__ void __launch_bounds__(256) k_bin_count_fv(SetupParams P, const float
     __syncthreads();  // block_add_256's partials are reused
     block_add_256(mine1, &P.vtot[B.n1]);
   }
-  if (lds) {
-    for (int i = threadIdx.x; i < P.T; i += blockDim.x)
-      if (hist[i]) atomicAdd(&P.cnt[(int64_t)B.n0 * P.T + i], hist[i]);
-  }
+  if (lds) hist_flush(P, hist, B.n0);
 }
 
 template <bool LDS>
@@ -479,65 +478,14 @@ __global__ void __launch_bounds__(256) k_bin_fill_fv(SetupParams P, int64_t Ftot
                                                      int64_t N) {
   extern __shared__ __attribute__((aligned(16))) int hist[];
   __shared__ int first32[MR_FV_NMAX];
-  const FvBlock B = fv_block_setup(nullptr, Ftot, first, N, first32, nullptr, false);
-  const bool lds = LDS && B.n0 == B.n1;
-  const int nq = P.clipz ? 2 : 1;
-  auto rec_q = [&](int64_t f, int q, FaceRec& r) -> bool {
-    r = P.recs[f];
-    if (q == 0) return true;
-    if (!(r.flags & FR_PAIR)) return false;
-    r = P.recs[P.NF + f];
-    return true;
-  };
-  if (lds) {
-    for (int i = threadIdx.x; i < P.T; i += blockDim.x) hist[i] = 0;
-    __syncthreads();
-    for (int k = 0; k < MR_FV_FPT; ++k) {
-      const int64_t lf = (int64_t)k * blockDim.x + threadIdx.x;
-      for (int q = 0; q < nq && lf < B.nf; ++q) {
-        FaceRec r;
-        int tx0, tx1, ty0, ty1;
-        if (rec_q(B.f0 + lf, q, r) && rec_tiles(P, r, tx0, tx1, ty0, ty1))
-          for (int ty = ty0; ty <= ty1; ++ty)
-            for (int tx = tx0; tx <= tx1; ++tx) atomicAdd(&hist[ty * P.TX + tx], 1);
-      }
-    }
-    __syncthreads();
-    const int vb = P.vbase[B.n0];
-    for (int i = threadIdx.x; i < P.T; i += blockDim.x)
-      if (hist[i]) hist[i] = vb + atomicAdd(&P.cur[(int64_t)B.n0 * P.T + i], hist[i]);  // reserve a block
-    __syncthreads();
-    for (int k = 0; k < MR_FV_FPT; ++k) {
-      const int64_t lf = (int64_t)k * blockDim.x + threadIdx.x;
-      for (int q = 0; q < nq && lf < B.nf; ++q) {
-        FaceRec r;
-        int tx0, tx1, ty0, ty1;
-        if (rec_q(B.f0 + lf, q, r) && rec_tiles(P, r, tx0, tx1, ty0, ty1))
-          for (int ty = ty0; ty <= ty1; ++ty)
-            for (int tx = tx0; tx <= tx1; ++tx) {
-              const int pos = atomicAdd(&hist[ty * P.TX + tx], 1);
-              if (pos < P.list_cap) P.list[pos] = (int)(B.f0 + lf + (q ? P.NF : 0));
-            }
-      }
-    }
-  } else {
+  const FvBlock B = fv_block_setup(nullptr, Ftot, first, N, first32, nullptr);
+  bin_fill_body(P, hist, LDS && B.n0 == B.n1, B.n0, [&](auto&& fn) {
     for (int k = 0; k < MR_FV_FPT; ++k) {
       const int64_t lf = (int64_t)k * blockDim.x + threadIdx.x;
       if (lf >= B.nf) break;
-      const int64_t f = B.f0 + lf;
-      const int n = fv_mesh(B, first32, first, N, f);
-      for (int q = 0; q < nq; ++q) {
-        FaceRec r;
-        int tx0, tx1, ty0, ty1;
-        if (rec_q(f, q, r) && rec_tiles(P, r, tx0, tx1, ty0, ty1))
-          for (int ty = ty0; ty <= ty1; ++ty)
-            for (int tx = tx0; tx <= tx1; ++tx) {
-              const int pos = P.vbase[n] + atomicAdd(&P.cur[(int64_t)n * P.T + ty * P.TX + tx], 1);
-              if (pos < P.list_cap) P.list[pos] = (int)(f + (q ? P.NF : 0));
-            }
-      }
+      fn(B.f0 + lf, fv_mesh(B, first32, first, N, B.f0 + lf));
     }
-  }
+  });
 }
 
 struct ScanParams {
@@ -675,9 +623,40 @@ MR_DEV uint32_t rec_rect(const SetupParams& P, const FaceRec& r) {
   return (uint32_t)tx0 | ((uint32_t)tx1 << 8) | ((uint32_t)ty0 << 16) | ((uint32_t)ty1 << 24);
 }
 
+// Vertex normals through the CSR vertex adjacency (entries (face << 2 | corner) sorted by (corner, face)); here
+// because k_bin_rect_world's row 0 is their first user (then k_setup_zero and k_vertex_normals).
+MR_DEV void face_normal(const float* verts, const int32_t* faces, int f, float nf[3]) {
+  const int32_t i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
+  float a[3], b[3];
+  for (int k = 0; k < 3; ++k) {
+    a[k] = verts[3 * i2 + k] - verts[3 * i1 + k];
+    b[k] = verts[3 * i0 + k] - verts[3 * i1 + k];
+  }
+  nf[0] = a[1] * b[2] - a[2] * b[1];
+  nf[1] = a[2] * b[0] - a[0] * b[2];
+  nf[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// verts_normals_packed for vertex v: the sum of its faces' (unnormalised) normals in CSR order
+// (the reference's index_add order), then F.normalize.
 MR_DEV void vertex_normal(const float* __restrict__ verts, const int32_t* __restrict__ faces,
                           const int32_t* __restrict__ ptr, const int32_t* __restrict__ adj, int64_t v,
-                          float* __restrict__ vn, float* __restrict__ vraw);
+                          float* __restrict__ vn, float* __restrict__ vraw) {
+  float s[3] = {0.f, 0.f, 0.f};
+  for (int e = ptr[v]; e < ptr[v + 1]; ++e) {
+    float nf[3];
+    face_normal(verts, faces, adj[e] >> 2, nf);
+    s[0] += nf[0];
+    s[1] += nf[1];
+    s[2] += nf[2];
+  }
+  float y[3], nrm, den;
+  normalize3(s, y, nrm, den);
+  for (int k = 0; k < 3; ++k) {
+    vn[3 * v + k] = y[k];
+    vraw[3 * v + k] = s[k];
+  }
+}
 // The fused forward's setup, world mode (the first launch of the per-view path): grid rows 1..N
 // project (face, view) pairs, one thread each; row 0, dispatched first (the CSR gathers are its
 // longest dependent chain), computes the vertex normals when the call asks for them (as
@@ -797,7 +776,8 @@ static_assert(sizeof(FaceRec) == 64, "FaceRec is staged as 4 float4");
   // 64 B apart) then land on distinct bank groups (4-way conflicts without the pad)
   __shared__ float4 s4[4 * 256 + 64];
   __shared__ float s9[9 * 256];
-  // view n's faces: mesh faces [fbase, fbase + Fv) -> records [rbase, rbase + Fv)
+  // view n's faces: mesh faces [fbase, fbase + Fv) -> records [rbase, rbase + Fv) (view_faces, spelled out:
+  // this kernel's code is kept as it was)
   int64_t Fv = F, rbase = (int64_t)n * F, fbase = 0;
   if (P.vff) {  // distinct meshes: view n renders mesh n (records = union faces)
     rbase = fbase = P.vff[n];
@@ -857,10 +837,7 @@ __global__ void __launch_bounds__(256) k_bin_rect_fv(SetupParams P, const float*
   const int64_t f0 = (int64_t)blockIdx.x * blockDim.x;
   if (blockIdx.x == 0 && threadIdx.x < CTR_COUNT) ctr[threadIdx.x] = 0;  // the work counters (k_bin_view)
   const int nf = (int)(Ftot - f0 < (int64_t)blockDim.x ? Ftot - f0 : (int64_t)blockDim.x);
-  const float4* src = (const float4*)(fv + 9 * f0);  // f0 % 256 == 0: 16-B aligned if fv is
-  const int n4 = ((uintptr_t)src & 15) == 0 ? 9 * nf / 4 : 0;
-  for (int i = threadIdx.x; i < n4; i += blockDim.x) ((float4*)sfv)[i] = src[i];
-  for (int i = 4 * n4 + threadIdx.x; i < 9 * nf; i += blockDim.x) sfv[i] = fv[9 * f0 + i];
+  stage_face_verts(fv, f0, nf, sfv);
   __syncthreads();
   if ((int)threadIdx.x >= nf) return;
   const int64_t f = f0 + threadIdx.x;

@@ -72,17 +72,8 @@ struct RasterBwdParams {
   float* gfv;
 };
 
-// One stored fragment (pixel px, py; slot pix; packed face f) of the modular raster backward:
-// the 9 face_verts gradients of face f in g.
-MR_DEV void raster_bwd_fragment_v(const RasterBwdParams& P, int px, int py, int64_t f, float gzp, const float (&gb)[3],
-                                  float gdp, float (&g)[3][3]);
-MR_DEV void raster_bwd_fragment(const RasterBwdParams& P, int px, int py, int64_t pix, int64_t f, float (&g)[3][3]) {
-  // an upstream gradient PyTorch passed as None arrives as NULL: zero
-  const float gb[3] = {P.gb ? P.gb[3 * pix] : 0.0f, P.gb ? P.gb[3 * pix + 1] : 0.0f, P.gb ? P.gb[3 * pix + 2] : 0.0f};
-  const float gzp = P.gz ? P.gz[pix] : 0.0f, gdp = P.gd ? P.gd[pix] : 0.0f;
-  raster_bwd_fragment_v(P, px, py, f, gzp, gb, gdp, g);
-}
-// The same from the fragment's upstream gradients given as values (gz, gb, gd).
+// One stored fragment (pixel px, py; packed face f) of the modular raster backward, its upstream
+// gradients given as values (gz, gb, gd): the 9 face_verts gradients of face f in g.
 MR_DEV void raster_bwd_fragment_v(const RasterBwdParams& P, int px, int py, int64_t f, float gzp, const float (&gb)[3],
                                   float gdp, float (&g)[3][3]) {
   FaceRec r;
@@ -126,6 +117,13 @@ MR_DEV void raster_bwd_fragment_v(const RasterBwdParams& P, int px, int py, int6
   } else {
     raster_bwd_pixel<false>(r, xf, yf, P.persp, P.clipb, gzp, gb, gdp, g);
   }
+}
+// The same with the upstream gradients read from slot pix.
+MR_DEV void raster_bwd_fragment(const RasterBwdParams& P, int px, int py, int64_t pix, int64_t f, float (&g)[3][3]) {
+  // an upstream gradient PyTorch passed as None arrives as NULL: zero
+  const float gb[3] = {P.gb ? P.gb[3 * pix] : 0.0f, P.gb ? P.gb[3 * pix + 1] : 0.0f, P.gb ? P.gb[3 * pix + 2] : 0.0f};
+  const float gzp = P.gz ? P.gz[pix] : 0.0f, gdp = P.gd ? P.gd[pix] : 0.0f;
+  raster_bwd_fragment_v(P, px, py, f, gzp, gb, gdp, g);
 }
 
 // One thread per stored fragment slot (n, y, x, k) in memory order: the loads of pix_to_face and

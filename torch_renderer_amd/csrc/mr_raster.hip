@@ -968,12 +968,11 @@ static int32_t render_backward(const mr_mesh_t* m, const float* vraw, const mr_v
   P.sgpix = w.sgpix;
   // no RGB gradient (a depth / silhouette render's backward): the geometry-only instantiation
   const bool geo = P.gRGB == nullptr;
-  // the drop-in Phong render (UV map with an 8-bit copy, point light, RGB, relu depth): the specialised one
+  // the drop-in Phong render with an RGB gradient, no near-plane clip, no vertex colours: the specialised one
 #ifndef MR_BWD_SPEC
 #define MR_BWD_SPEC 1
 #endif
-  const bool spec = MR_BWD_SPEC && !geo && !vcol && !s->clip_z && m->tex_kind == 2 && m->tex_u8 && m->tex_lut &&
-                    sp->light_kind == 0 && sp->rgb_channels == 3 && !(sp->out_flags & (MR_OUT_ZBUF | MR_OUT_SIL_RGBA));
+  const bool spec = MR_BWD_SPEC && drop_in_shading(P.S, sp->rgb_channels, sp->out_flags) && !geo && !vcol && !s->clip_z;
   switch (spec ? 8 : (vcol ? 1 : 0) | (s->clip_z ? 2 : 0) | (geo ? 4 : 0)) {
     case 0: rc = launch_bwd_fused<18, false>(P, NT, st); break;
     case 1: rc = launch_bwd_fused<27, false>(P, NT, st); break;

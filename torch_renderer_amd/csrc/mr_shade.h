@@ -191,7 +191,6 @@ MR_DEV void tex_taps(const ShadeParams& S, int x0, int y0, float4& a, float4& b,
 // so that, given bitwise-equal barycentrics, the cell is the oracle's: a contracted (FMA) position
 // one ulp off a texel boundary picks the neighbouring cell and a different gradient. The weights and
 // the blend after it are continuous in the position and keep fast arithmetic.
-MR_DEV void tex_blend(const ShadeParams& S, const TexTap& t, float out[3], bool lut);
 // The sample position of (u, v) (tex_sample's first half): the cell, its weights' inputs and the border flags.
 MR_DEV void tex_locate(const ShadeParams& S, float u, float v, TexTap& t) {
   const float gx = u * 2.0f - 1.0f, gy = v * 2.0f - 1.0f;
@@ -207,16 +206,7 @@ MR_DEV void tex_locate(const ShadeParams& S, float u, float v, TexTap& t) {
   t.y0 = (int)floorf(iy);
   t.pre = false;
 }
-// SPEC (specialised kernels): the map is known to have an 8-bit copy (S.tex8 non-null).
-template <int SPEC = 0>
-MR_DEV void tex_sample(const ShadeParams& S, float u, float v, float out[3], TexTap& t, bool lut = false) {
-  tex_locate(S, u, v, t);
-  if (SPEC || S.tex8) {  // the raw texels stay in the tap: a backward's second look-up (tex_sample_bwd) reloads nothing
-    tex_taps_raw(S, t.x0, t.y0, t.raw);
-    t.pre = true;
-  }
-  tex_blend(S, t, out, lut);
-}
+// The bilinear blend of the located cell's four taps (tex_sample's second half).
 MR_DEV void tex_blend(const ShadeParams& S, const TexTap& t, float out[3], bool lut) {
   MR_FP_FAST
   const float ix = t.ix, iy = t.iy;
@@ -229,6 +219,16 @@ MR_DEV void tex_blend(const ShadeParams& S, const TexTap& t, float out[3], bool 
   out[0] = ((a.x * nw + b.x * ne) + c.x * sw) + d.x * se;
   out[1] = ((a.y * nw + b.y * ne) + c.y * sw) + d.y * se;
   out[2] = ((a.z * nw + b.z * ne) + c.z * sw) + d.z * se;
+}
+// SPEC (specialised kernels): the map is known to have an 8-bit copy (S.tex8 non-null).
+template <int SPEC = 0>
+MR_DEV void tex_sample(const ShadeParams& S, float u, float v, float out[3], TexTap& t, bool lut = false) {
+  tex_locate(S, u, v, t);
+  if (SPEC || S.tex8) {  // the raw texels stay in the tap: a backward's second look-up (tex_sample_bwd) reloads nothing
+    tex_taps_raw(S, t.x0, t.y0, t.raw);
+    t.pre = true;
+  }
+  tex_blend(S, t, out, lut);
 }
 // d(texel)/d(u,v) contracted with g (3 channels) -> (gu, gv)
 MR_DEV void tex_sample_bwd(const ShadeParams& S, const TexTap& t, const float g[3], float& gu, float& gv,
@@ -393,23 +393,137 @@ MR_DEV float interp3_ieee(float b0, float b1, float b2, float a0, float a1, floa
   return (b0 * a0 + b1 * a1) + b2 * a2;
 }
 
-// Intermediate values kept for the backward pass.
-struct ShadeCache {
+// ---------------- Phong colour of one fragment ----------------
+// phong_shading for one (pixel, k) fragment: colour = (ambient + diffuse) * texel + specular, without
+// the blend (shade_fwd blends K = 1; softmax_rgb_blend over K fragments is the K-deep shader's).
+// b = original-face barycentrics. SPEC 1: the drop-in Phong render's constants (drop_in_shading).
+struct PhongCache {
   float P[3], Nn[3], nh[3], nlen, nden, l[3], lh[3], llen, lden, v[3], vh[3], vlen, vden;
-  float cosd, r[3], vr, as, spow, texel[3], amb[3], diff[3], spec[3], col[3];
-  float ps, pc, zi, zimax, E, w, ex, delta, den;
-  float qs, qc;  // 1 - ps, 1 - pc (unmasked: the derivatives' factor; sigmoid2)
+  float cosd, r[3], vr, as, texel[3], amb[3], diff[3];
   TexTap tap;
 };
+
+template <int SPEC = 0>
+MR_DEV void phong_fwd(const ShadeParams& S, int n, const PixGeom& G, float b0, float b1, float b2, float col[3],
+                      PhongCache& C, bool lut = false) {
+  MR_FP_FAST
+  const int tex_kind = SPEC ? 2 : S.tex_kind, light_kind = SPEC ? 0 : S.light_kind;
+  for (int k = 0; k < 3; ++k) {
+    C.P[k] = interp3(b0, b1, b2, G.X[0][k], G.X[1][k], G.X[2][k]);
+    C.amb[k] = S.mat_amb[k] * S.light_amb[k];
+  }
+  if (tex_kind == 2) {
+    const float u = interp3_ieee(b0, b1, b2, G.uv[0][0], G.uv[1][0], G.uv[2][0]);
+    const float v = interp3_ieee(b0, b1, b2, G.uv[0][1], G.uv[1][1], G.uv[2][1]);
+    tex_sample<SPEC>(S, u, v, C.texel, C.tap, lut);
+  } else if (tex_kind == 1) {
+    for (int k = 0; k < 3; ++k) C.texel[k] = interp3(b0, b1, b2, G.col[0][k], G.col[1][k], G.col[2][k]);
+  } else {
+    C.texel[0] = C.texel[1] = C.texel[2] = 1.0f;
+  }
+  float spec[3] = {0.f, 0.f, 0.f};
+  if (light_kind == 0) {
+    for (int k = 0; k < 3; ++k) C.Nn[k] = interp3(b0, b1, b2, G.Nv[0][k], G.Nv[1][k], G.Nv[2][k]);
+    normalize3(C.Nn, C.nh, C.nlen, C.nden);
+    for (int k = 0; k < 3; ++k) C.l[k] = S.light_loc[k] - C.P[k];
+    normalize3(C.l, C.lh, C.llen, C.lden);
+    C.cosd = dot3(C.nh, C.lh);
+    const float angle = C.cosd > 0.0f ? C.cosd : 0.0f;
+    const float* cc = S.cam_centers + (int64_t)n * S.cam_center_stride;
+    for (int k = 0; k < 3; ++k) C.v[k] = cc[k] - C.P[k];
+    normalize3(C.v, C.vh, C.vlen, C.vden);
+    for (int k = 0; k < 3; ++k) C.r[k] = -C.lh[k] + 2.0f * (C.cosd * C.nh[k]);
+    C.vr = dot3(C.vh, C.r);
+    C.as = (C.vr > 0.0f ? C.vr : 0.0f) * (C.cosd > 0.0f ? 1.0f : 0.0f);
+    const float spow = fpow(C.as, S.shininess);
+    for (int k = 0; k < 3; ++k) {
+      C.diff[k] = S.mat_diff[k] * (S.light_diff[k] * angle);
+      spec[k] = S.mat_spec[k] * (S.light_spec[k] * spow);
+    }
+  } else {
+    for (int k = 0; k < 3; ++k) C.diff[k] = 0.0f;
+  }
+  for (int k = 0; k < 3; ++k) col[k] = (C.amb[k] + C.diff[k]) * C.texel[k] + spec[k];
+}
+
+// Backward of phong_fwd given the colour gradient gcol: gradients w.r.t. the interpolated world point
+// (gP), the interpolated (unnormalised) normal (gNn), the texel (gtex) and the interpolated uv (guv; UV
+// textures), and the colour's part of the barycentrics' gradient ADDED to gb (the caller initialises it).
+template <int SPEC = 0>
+MR_DEV void phong_bwd(const ShadeParams& S, const PixGeom& G, const PhongCache& C, const float gcol[3], float gb[3],
+                      float gP[3], float gNn[3], float gtex[3], float guv[2], bool lut = false) {
+  MR_FP_FAST
+  const int tex_kind = SPEC ? 2 : S.tex_kind, light_kind = SPEC ? 0 : S.light_kind;
+  for (int k = 0; k < 3; ++k) {
+    gtex[k] = gcol[k] * (C.amb[k] + C.diff[k]);
+    gP[k] = gNn[k] = 0.0f;
+  }
+  if (light_kind == 0) {
+    float gangle = 0.0f, gspow = 0.0f;
+    for (int k = 0; k < 3; ++k) {
+      gangle += gcol[k] * C.texel[k] * S.mat_diff[k] * S.light_diff[k];
+      gspow += gcol[k] * S.mat_spec[k] * S.light_spec[k];
+    }
+    const float gas = (C.as > 0.0f) ? gspow * S.shininess * fpow(C.as, S.shininess - 1.0f) : 0.0f;
+    const float ms = C.cosd > 0.0f ? 1.0f : 0.0f;
+    const float gvr = (C.vr > 0.0f) ? gas * ms : 0.0f;
+    float gvh[3], gr[3], glh[3], gnh[3];
+    for (int k = 0; k < 3; ++k) {
+      gvh[k] = gvr * C.r[k];
+      gr[k] = gvr * C.vh[k];
+    }
+    // r = -lh + 2 * (cos * nh)
+    float gcos = 2.0f * dot3(gr, C.nh);
+    for (int k = 0; k < 3; ++k) {
+      glh[k] = -gr[k];
+      gnh[k] = 2.0f * C.cosd * gr[k];
+    }
+    gcos += (C.cosd > 0.0f) ? gangle : 0.0f;  // relu(cos) for diffuse
+    for (int k = 0; k < 3; ++k) {
+      gnh[k] += gcos * C.lh[k];
+      glh[k] += gcos * C.nh[k];
+    }
+    float gl[3], gvv[3];
+    normalize3_bwd(C.Nn, C.nlen, C.nden, gnh, gNn);
+    normalize3_bwd(C.l, C.llen, C.lden, glh, gl);
+    normalize3_bwd(C.v, C.vlen, C.vden, gvh, gvv);
+    for (int k = 0; k < 3; ++k) gP[k] = -gl[k] - gvv[k];
+  }
+  guv[0] = guv[1] = 0.0f;
+  for (int c = 0; c < 3; ++c) {
+    gb[c] += dot3(G.X[c], gP);
+    if (light_kind == 0) gb[c] += dot3(G.Nv[c], gNn);
+  }
+  if (tex_kind == 2) {
+    tex_sample_bwd(S, C.tap, gtex, guv[0], guv[1], lut);
+    for (int c = 0; c < 3; ++c) gb[c] += G.uv[c][0] * guv[0] + G.uv[c][1] * guv[1];
+  } else if (tex_kind == 1) {
+    for (int c = 0; c < 3; ++c) gb[c] += dot3(G.col[c], gtex);
+  }
+}
+
+// Intermediate values of shade_fwd kept for the backward pass: the colour's and the K = 1 blend's.
+struct ShadeCache : PhongCache {
+  float col[3];
+  float ps, pc, zi, zimax, E, w, ex, delta, den;
+  float qs, qc;  // 1 - ps, 1 - pc (unmasked: the derivatives' factor; sigmoid2)
+};
+
+// What the SPEC = 1 instantiations (phong_fwd / phong_bwd, shade_fwd / shade_bwd, tex_sample, bwd_slot_inputs)
+// hard-code, stated once for the host's two launch sites (launch_shade_render, render_backward): a UV texture
+// with an 8-bit copy, a point light, three RGB channels, relu depth (no MR_OUT_ZBUF) and a one-channel
+// silhouette (no MR_OUT_SIL_RGBA). Each site adds the conditions of its own kernel.
+static inline bool drop_in_shading(const ShadeParams& S, int rgb_channels, int out_flags) {
+  return S.tex_kind == 2 && S.tex8 && S.light_kind == 0 && rgb_channels == 3 &&
+         !(out_flags & (MR_OUT_ZBUF | MR_OUT_SIL_RGBA));
+}
 
 // Forward shading of one pixel (hit = face found). b = bary (after clip), z, sd = signed dist.
 template <int SPEC = 0>
 MR_DEV void shade_fwd(const ShadeParams& S, int n, bool hit, const PixGeom& G, float b0, float b1, float b2,
                       float z, float sd, ShadeOut& o, ShadeCache& C, bool lut = false) {
   MR_FP_FAST
-  // SPEC 1: UV map with an 8-bit copy, point light, relu depth (the drop-in Phong render: compile-time
-  // constants instead of the runtime switches)
-  const int tex_kind = SPEC ? 2 : S.tex_kind, light_kind = SPEC ? 0 : S.light_kind;
+  // SPEC 1: the drop-in Phong render (drop_in_shading): compile-time constants instead of the runtime switches
   const int zbuf_mode = SPEC ? 0 : S.zbuf_mode;
   const float m = hit ? 1.0f : 0.0f;
   const float zb = hit ? z : -1.0f;    // zbuf background = -1
@@ -422,44 +536,7 @@ MR_DEV void shade_fwd(const ShadeParams& S, int n, bool hit, const PixGeom& G, f
   o.sil = 1.0f - (1.0f - C.ps);
   // Phong colours (only meaningful for hit pixels; background weight is 0)
   for (int k = 0; k < 3; ++k) C.col[k] = 0.0f;
-  if (hit) {
-    for (int k = 0; k < 3; ++k) {
-      C.P[k] = interp3(b0, b1, b2, G.X[0][k], G.X[1][k], G.X[2][k]);
-      C.amb[k] = S.mat_amb[k] * S.light_amb[k];
-    }
-    if (tex_kind == 2) {
-      const float u = interp3_ieee(b0, b1, b2, G.uv[0][0], G.uv[1][0], G.uv[2][0]);
-      const float v = interp3_ieee(b0, b1, b2, G.uv[0][1], G.uv[1][1], G.uv[2][1]);
-      tex_sample<SPEC>(S, u, v, C.texel, C.tap, lut);
-    } else if (tex_kind == 1) {
-      for (int k = 0; k < 3; ++k) C.texel[k] = interp3(b0, b1, b2, G.col[0][k], G.col[1][k], G.col[2][k]);
-    } else {
-      C.texel[0] = C.texel[1] = C.texel[2] = 1.0f;
-    }
-    if (light_kind == 0) {
-      for (int k = 0; k < 3; ++k) C.Nn[k] = interp3(b0, b1, b2, G.Nv[0][k], G.Nv[1][k], G.Nv[2][k]);
-      normalize3(C.Nn, C.nh, C.nlen, C.nden);
-      for (int k = 0; k < 3; ++k) C.l[k] = S.light_loc[k] - C.P[k];
-      normalize3(C.l, C.lh, C.llen, C.lden);
-      C.cosd = dot3(C.nh, C.lh);
-      const float angle = C.cosd > 0.0f ? C.cosd : 0.0f;
-      const float* cc = S.cam_centers + (int64_t)n * S.cam_center_stride;
-      for (int k = 0; k < 3; ++k) C.v[k] = cc[k] - C.P[k];
-      normalize3(C.v, C.vh, C.vlen, C.vden);
-      for (int k = 0; k < 3; ++k) C.r[k] = -C.lh[k] + 2.0f * (C.cosd * C.nh[k]);
-      C.vr = dot3(C.vh, C.r);
-      const float ms = C.cosd > 0.0f ? 1.0f : 0.0f;
-      C.as = (C.vr > 0.0f ? C.vr : 0.0f) * ms;
-      C.spow = fpow(C.as, S.shininess);
-      for (int k = 0; k < 3; ++k) {
-        C.diff[k] = S.mat_diff[k] * (S.light_diff[k] * angle);
-        C.spec[k] = S.mat_spec[k] * (S.light_spec[k] * C.spow);
-      }
-    } else {
-      for (int k = 0; k < 3; ++k) C.diff[k] = C.spec[k] = 0.0f;
-    }
-    for (int k = 0; k < 3; ++k) C.col[k] = (C.amb[k] + C.diff[k]) * C.texel[k] + C.spec[k];
-  }
+  if (hit) phong_fwd<SPEC>(S, n, G, b0, b1, b2, C.col, C, lut);
   // softmax_rgb_blend (K = 1)
   const float eps = 1e-10f;
   sigmoid2((-dd) * S.inv_sigma_rgb, C.pc, C.qc);
@@ -490,8 +567,7 @@ MR_DEV void shade_bwd(const ShadeParams& S, const PixGeom& G, float b0, float b1
                       const ShadeCache& C, float gD, float gS, const float gRGB[3], float gA, ShadeGrad& R,
                       bool lut = false) {
   MR_FP_FAST
-  const int tex_kind = SPEC ? 2 : S.tex_kind, light_kind = SPEC ? 0 : S.light_kind;  // (as shade_fwd)
-  const int zbuf_mode = SPEC ? 0 : S.zbuf_mode;
+  const int zbuf_mode = SPEC ? 0 : S.zbuf_mode;  // (as shade_fwd)
   const float b[3] = {b0, b1, b2};
   R.gz = 0.0f;
   R.gsd = 0.0f;
@@ -538,62 +614,20 @@ MR_DEV void shade_bwd(const ShadeParams& S, const PixGeom& G, float b0, float b1
     R.gsd += -(gx * S.inv_sigma_rgb);
   }
   // colours = (amb + diff) * texel + spec
-  float gtex[3], gP[3] = {0.f, 0.f, 0.f}, gNn[3] = {0.f, 0.f, 0.f};
-  for (int k = 0; k < 3; ++k) gtex[k] = gcol[k] * (C.amb[k] + C.diff[k]);
-  if (light_kind == 0) {
-    float gangle = 0.0f, gspow = 0.0f;
-    for (int k = 0; k < 3; ++k) {
-      gangle += gcol[k] * C.texel[k] * S.mat_diff[k] * S.light_diff[k];
-      gspow += gcol[k] * S.mat_spec[k] * S.light_spec[k];
-    }
-    const float gas = (C.as > 0.0f) ? gspow * S.shininess * fpow(C.as, S.shininess - 1.0f) : 0.0f;
-    const float ms = C.cosd > 0.0f ? 1.0f : 0.0f;
-    const float gvr = (C.vr > 0.0f) ? gas * ms : 0.0f;
-    float gvh[3], gr[3], glh[3], gnh[3];
-    for (int k = 0; k < 3; ++k) {
-      gvh[k] = gvr * C.r[k];
-      gr[k] = gvr * C.vh[k];
-    }
-    // r = -lh + 2 * (cos * nh)
-    float gcos = 2.0f * dot3(gr, C.nh);
-    for (int k = 0; k < 3; ++k) {
-      glh[k] = -gr[k];
-      gnh[k] = 2.0f * C.cosd * gr[k];
-    }
-    gcos += (C.cosd > 0.0f) ? gangle : 0.0f;  // relu(cos) for diffuse
-    for (int k = 0; k < 3; ++k) {
-      gnh[k] += gcos * C.lh[k];
-      glh[k] += gcos * C.nh[k];
-    }
-    float gl[3], gvv[3];
-    normalize3_bwd(C.Nn, C.nlen, C.nden, gnh, gNn);
-    normalize3_bwd(C.l, C.llen, C.lden, glh, gl);
-    normalize3_bwd(C.v, C.vlen, C.vden, gvh, gvv);
-    for (int k = 0; k < 3; ++k) gP[k] = -gl[k] - gvv[k];
-  }
+  float gtex[3], gP[3], gNn[3], guv[2];
+  phong_bwd<SPEC>(S, G, C, gcol, R.gb, gP, gNn, gtex, guv, lut);
+  const bool vcol = !SPEC && S.tex_kind == 1;
   for (int k = 0; k < 3; ++k) {
     R.gP[k] = gP[k];
     R.gNn[k] = gNn[k];
-    R.gtex[k] = tex_kind == 1 ? gtex[k] : 0.0f;
+    R.gtex[k] = vcol ? gtex[k] : 0.0f;
   }
-  for (int c = 0; c < 3; ++c) {
-    R.gb[c] += dot3(G.X[c], gP);
-    if (light_kind == 0) R.gb[c] += dot3(G.Nv[c], gNn);
+  for (int c = 0; c < 3; ++c)
     for (int k = 0; k < 3; ++k) {
       R.gX[c][k] = b[c] * gP[k];
       R.gN[c][k] = b[c] * gNn[k];
+      if (vcol) R.gC[c][k] = b[c] * gtex[k];
     }
-  }
-  if (tex_kind == 2) {
-    float gu, gv;
-    tex_sample_bwd(S, C.tap, gtex, gu, gv, lut);
-    for (int c = 0; c < 3; ++c) R.gb[c] += G.uv[c][0] * gu + G.uv[c][1] * gv;
-  } else if (tex_kind == 1) {
-    for (int c = 0; c < 3; ++c) {
-      R.gb[c] += dot3(G.col[c], gtex);
-      for (int k = 0; k < 3; ++k) R.gC[c][k] = b[c] * gtex[k];
-    }
-  }
 }
 
 // ---------------- rasterizer backward (geometry_utils.h) ----------------
@@ -806,109 +840,7 @@ MR_DEV void project_bwd(const ViewRec& V, const float X[3], const float gn[3], f
   for (int bb = 0; bb < 3; ++bb) gT[bb] += gv[bb];
 }
 
-// ---------------- per-fragment Phong colour (K-deep soft shading) ----------------
-// phong_shading for one (pixel, k) fragment: colour = (ambient + diffuse) * texel + specular,
-// the same terms as shade_fwd's colour part, without the blend (softmax_rgb_blend couples the K
-// fragments and is done by the caller). b = original-face barycentrics.
-struct PhongCache {
-  float P[3], Nn[3], nh[3], nlen, nden, l[3], lh[3], llen, lden, v[3], vh[3], vlen, vden;
-  float cosd, r[3], vr, as, texel[3], amb[3], diff[3];
-  TexTap tap;
-};
-
-MR_DEV void phong_fwd(const ShadeParams& S, int n, const PixGeom& G, float b0, float b1, float b2, float col[3],
-                      PhongCache& C) {
-  MR_FP_FAST
-  for (int k = 0; k < 3; ++k) {
-    C.P[k] = interp3(b0, b1, b2, G.X[0][k], G.X[1][k], G.X[2][k]);
-    C.amb[k] = S.mat_amb[k] * S.light_amb[k];
-  }
-  if (S.tex_kind == 2) {
-    const float u = interp3_ieee(b0, b1, b2, G.uv[0][0], G.uv[1][0], G.uv[2][0]);
-    const float v = interp3_ieee(b0, b1, b2, G.uv[0][1], G.uv[1][1], G.uv[2][1]);
-    tex_sample(S, u, v, C.texel, C.tap);
-  } else if (S.tex_kind == 1) {
-    for (int k = 0; k < 3; ++k) C.texel[k] = interp3(b0, b1, b2, G.col[0][k], G.col[1][k], G.col[2][k]);
-  } else {
-    C.texel[0] = C.texel[1] = C.texel[2] = 1.0f;
-  }
-  float spec[3] = {0.f, 0.f, 0.f};
-  if (S.light_kind == 0) {
-    for (int k = 0; k < 3; ++k) C.Nn[k] = interp3(b0, b1, b2, G.Nv[0][k], G.Nv[1][k], G.Nv[2][k]);
-    normalize3(C.Nn, C.nh, C.nlen, C.nden);
-    for (int k = 0; k < 3; ++k) C.l[k] = S.light_loc[k] - C.P[k];
-    normalize3(C.l, C.lh, C.llen, C.lden);
-    C.cosd = dot3(C.nh, C.lh);
-    const float angle = C.cosd > 0.0f ? C.cosd : 0.0f;
-    const float* cc = S.cam_centers + (int64_t)n * S.cam_center_stride;
-    for (int k = 0; k < 3; ++k) C.v[k] = cc[k] - C.P[k];
-    normalize3(C.v, C.vh, C.vlen, C.vden);
-    for (int k = 0; k < 3; ++k) C.r[k] = -C.lh[k] + 2.0f * (C.cosd * C.nh[k]);
-    C.vr = dot3(C.vh, C.r);
-    C.as = (C.vr > 0.0f ? C.vr : 0.0f) * (C.cosd > 0.0f ? 1.0f : 0.0f);
-    const float spow = fpow(C.as, S.shininess);
-    for (int k = 0; k < 3; ++k) {
-      C.diff[k] = S.mat_diff[k] * (S.light_diff[k] * angle);
-      spec[k] = S.mat_spec[k] * (S.light_spec[k] * spow);
-    }
-  } else {
-    for (int k = 0; k < 3; ++k) C.diff[k] = 0.0f;
-  }
-  for (int k = 0; k < 3; ++k) col[k] = (C.amb[k] + C.diff[k]) * C.texel[k] + spec[k];
-}
-
-// Backward of phong_fwd given the colour gradient gcol: gradients w.r.t. the barycentrics (gb),
-// the interpolated world point (gP), the interpolated (unnormalised) normal (gNn), the texel
-// (gtex) and the interpolated uv (guv; UV textures).
-MR_DEV void phong_bwd(const ShadeParams& S, const PixGeom& G, const PhongCache& C, const float gcol[3], float gb[3],
-                      float gP[3], float gNn[3], float gtex[3], float guv[2]) {
-  MR_FP_FAST
-  for (int k = 0; k < 3; ++k) {
-    gtex[k] = gcol[k] * (C.amb[k] + C.diff[k]);
-    gP[k] = gNn[k] = 0.0f;
-  }
-  if (S.light_kind == 0) {
-    float gangle = 0.0f, gspow = 0.0f;
-    for (int k = 0; k < 3; ++k) {
-      gangle += gcol[k] * C.texel[k] * S.mat_diff[k] * S.light_diff[k];
-      gspow += gcol[k] * S.mat_spec[k] * S.light_spec[k];
-    }
-    const float gas = (C.as > 0.0f) ? gspow * S.shininess * fpow(C.as, S.shininess - 1.0f) : 0.0f;
-    const float gvr = (C.vr > 0.0f && C.cosd > 0.0f) ? gas : 0.0f;
-    float gvh[3], gr[3], glh[3], gnh[3];
-    for (int k = 0; k < 3; ++k) {
-      gvh[k] = gvr * C.r[k];
-      gr[k] = gvr * C.vh[k];
-    }
-    float gcos = 2.0f * dot3(gr, C.nh);
-    for (int k = 0; k < 3; ++k) {
-      glh[k] = -gr[k];
-      gnh[k] = 2.0f * C.cosd * gr[k];
-    }
-    gcos += (C.cosd > 0.0f) ? gangle : 0.0f;
-    for (int k = 0; k < 3; ++k) {
-      gnh[k] += gcos * C.lh[k];
-      glh[k] += gcos * C.nh[k];
-    }
-    float gl[3], gvv[3];
-    normalize3_bwd(C.Nn, C.nlen, C.nden, gnh, gNn);
-    normalize3_bwd(C.l, C.llen, C.lden, glh, gl);
-    normalize3_bwd(C.v, C.vlen, C.vden, gvh, gvv);
-    for (int k = 0; k < 3; ++k) gP[k] = -gl[k] - gvv[k];
-  }
-  guv[0] = guv[1] = 0.0f;
-  for (int c = 0; c < 3; ++c) {
-    gb[c] = dot3(G.X[c], gP);
-    if (S.light_kind == 0) gb[c] += dot3(G.Nv[c], gNn);
-  }
-  if (S.tex_kind == 2) {
-    tex_sample_bwd(S, C.tap, gtex, guv[0], guv[1]);
-    for (int c = 0; c < 3; ++c) gb[c] += G.uv[c][0] * guv[0] + G.uv[c][1] * guv[1];
-  } else if (S.tex_kind == 1) {
-    for (int c = 0; c < 3; ++c) gb[c] += dot3(G.col[c], gtex);
-  }
-}
-
+// ---------------- texture-map gradient (K-deep soft shading) ----------------
 // Gradient of the bilinear texel w.r.t. the (flipped, RGBA-padded) map: the four taps' weights
 // times gtex, added into gmap (Ht, Wt, 4) with float atomics (taps outside the map carry none).
 MR_DEV void tex_map_bwd(const ShadeParams& S, const TexTap& t, const float gtex[3], float* __restrict__ gmap) {

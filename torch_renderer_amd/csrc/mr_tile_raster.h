@@ -97,36 +97,10 @@ MR_DEV int kth_bit(unsigned long long m, int k) {
   return pos;
 }
 
-MR_DEV bool frag_keep(const FaceRec& r, float x, float y, float pad, float blur, bool persp, bool clipb,
-                      bool fast, float& pz) {
-  if (x > r.xmax + pad || x < r.xmin - pad || y > r.ymax + pad || y < r.ymin - pad) return false;
-  const float e0 = edge_fn(x, y, r.x1, r.y1, r.x2, r.y2);
-  const float e1 = edge_fn(x, y, r.x2, r.y2, r.x0, r.y0);
-  const float e2 = edge_fn(x, y, r.x0, r.y0, r.x1, r.y1);
-  if (fast) {
-    const bool inp = (e0 > 0.0f) & (e1 > 0.0f) & (e2 > 0.0f);
-    const bool inn = (e0 < 0.0f) & (e1 < 0.0f) & (e2 < 0.0f);
-    if (!(r.area > 0.0f ? inp : inn)) return false;
-  }
-  const float w0 = e0 / r.area, w1 = e1 / r.area, w2 = e2 / r.area;
-  float c0, c1, c2, b0, b1, b2;
-  if (persp) persp_fwd(w0, w1, w2, r.z0, r.z1, r.z2, c0, c1, c2);
-  else { c0 = w0; c1 = w1; c2 = w2; }
-  if (clipb) clip_fwd(c0, c1, c2, b0, b1, b2);
-  else { b0 = c0; b1 = c1; b2 = c2; }
-  pz = b0 * r.z0 + b1 * r.z1 + b2 * r.z2;
-  if (pz < 0.0f) return false;
-  const bool inside = c0 > 0.0f && c1 > 0.0f && c2 > 0.0f;
-  if (!inside) {
-    if (!(blur > 0.0f)) return false;
-    if (pt_tri_dist(x, y, r) >= blur) return false;
-  }
-  return true;
-}
-
-// frag_keep split in two for callers that can reject on the depth key first (k_raster_kp): the part
-// up to the depth (bbox, edge signs, divisions, pz >= 0), with the inside flag; the caller then keeps
-// the fragment iff inside || (blur > 0 && !(pt_tri_dist >= blur)) — frag_keep's decision exactly.
+// The part of the per-(pixel, face) decision up to the depth: bbox, edge signs, divisions, perspective and
+// clip corrections, pz >= 0, with the inside flag. Callers that can reject on the depth key first
+// (k_raster_kp) stop here and keep the fragment iff inside || (blur > 0 && !(pt_tri_dist >= blur)),
+// which is frag_keep's decision exactly.
 MR_DEV bool frag_depth(const FaceRec& r, float x, float y, float pad, bool persp, bool clipb, bool fast, float& pz,
                        bool& inside) {
   if (x > r.xmax + pad || x < r.xmin - pad || y > r.ymax + pad || y < r.ymin - pad) return false;
@@ -150,6 +124,17 @@ MR_DEV bool frag_depth(const FaceRec& r, float x, float y, float pad, bool persp
   return true;
 }
 
+MR_DEV bool frag_keep(const FaceRec& r, float x, float y, float pad, float blur, bool persp, bool clipb,
+                      bool fast, float& pz) {
+  bool inside;
+  if (!frag_depth(r, x, y, pad, persp, clipb, fast, pz, inside)) return false;
+  if (!inside) {
+    if (!(blur > 0.0f)) return false;
+    if (pt_tri_dist(x, y, r) >= blur) return false;
+  }
+  return true;
+}
+
 #define MR_NONE 0x7fffffff  // "no face" sentinel, larger than any face code
 
 // Sort code of a record id: upstream's clipped packed order puts the two triangles of a split
@@ -168,32 +153,6 @@ MR_DEV int rec_orig(int id, int64_t NF) { return id >= NF ? (int)(id - NF) : id;
 // pair as one candidate): if both are kept the second replaces the first iff its distance to the
 // pixel is smaller than the first's |signed distance|; else whichever is kept. Returns the record
 // id and depth of the candidate.
-MR_DEV bool pair_keep(const FaceRec* __restrict__ recs, int64_t NF, int id, const FaceRec& r, float x, float y,
-                      float pad, float blur, bool persp, bool clipb, int& cid, float& pz);
-// The pixels of one lane's tile rectangle for a split face's triangle (k_tile_raster, rare path;
-// out of line so that its registers do not weigh on the pixel-pair loop).
-// A wave's staged face records (one per entry lane), structure-of-arrays: field i of record m at
-// rec[i][m]. (Measured against 80-B padded array-of-structures records read with ds_read_b128: no gain,
-// profiles/r4f_bands_ab.txt.)
-struct StageRecs {
-  float rec[16][64];
-};
-MR_DEV void stage_rec_put(StageRecs& S, int lane, const FaceRec& r) {
-  const float* f = (const float*)&r;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) S.rec[i][lane] = f[i];
-}
-MR_DEV FaceRec stage_rec_get(const StageRecs& S, int m) {
-  FaceRec r;
-  float* f = (float*)&r;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) f[i] = S.rec[i][m];
-  return r;
-}
-__attribute__((noinline)) __device__ void raster_pair_rect(const FaceRec* __restrict__ recs, int64_t NF,
-                                                           const StageRecs& srec, const int* sid, const float* xs,
-                                                           const float* ys, unsigned long long* key, int lane,
-                                                           int prect, float pad, float blur, bool persp, bool clipb);
 MR_DEV bool pair_keep(const FaceRec* __restrict__ recs, int64_t NF, int id, const FaceRec& r, float x, float y,
                       float pad, float blur, bool persp, bool clipb, int& cid, float& pz) {
   const bool second = id >= NF;
@@ -219,6 +178,24 @@ MR_DEV bool pair_keep(const FaceRec* __restrict__ recs, int64_t NF, int id, cons
   return false;
 }
 
+// A wave's staged face records (one per entry lane), structure-of-arrays: field i of record m at
+// rec[i][m]. (Measured against 80-B padded array-of-structures records read with ds_read_b128: no gain,
+// profiles/r4f_bands_ab.txt.)
+struct StageRecs {
+  float rec[16][64];
+};
+MR_DEV void stage_rec_put(StageRecs& S, int lane, const FaceRec& r) {
+  const float* f = (const float*)&r;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) S.rec[i][lane] = f[i];
+}
+MR_DEV FaceRec stage_rec_get(const StageRecs& S, int m) {
+  FaceRec r;
+  float* f = (float*)&r;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) f[i] = S.rec[i][m];
+  return r;
+}
 // (z, face) packed so that unsigned order == frag_less order on the depths that are ever
 // kept (pz >= 0; -0 folds onto +0, which the CPU compares equal). The empty key sorts
 // after every kept fragment, +inf depth included.
@@ -560,6 +537,8 @@ __global__ void __launch_bounds__(1024) k_bin_view(ViewBinParams P, FwdParams F)
   }
 }
 
+// The pixels of one lane's tile rectangle for a split face's triangle (k_tile_raster, rare path;
+// out of line so that its registers do not weigh on the pixel-pair loop).
 __attribute__((noinline)) __device__ void raster_pair_rect(const FaceRec* __restrict__ recs, int64_t NF,
                                                            const StageRecs& srec, const int* sid, const float* xs,
                                                            const float* ys, unsigned long long* key, int lane,
@@ -830,10 +809,6 @@ __global__ void __launch_bounds__(256) k_shade_rec(ShadeParams S, int64_t F, Sha
   make_shade_rec(S, (uint32_t)f, R);
   out[f] = R;
 }
-
-MR_DEV void vertex_normal(const float* __restrict__ verts, const int32_t* __restrict__ faces,
-                          const int32_t* __restrict__ ptr, const int32_t* __restrict__ adj, int64_t v,
-                          float* __restrict__ vn, float* __restrict__ vraw);
 
 // The fused forward's first kernel: blocks [0, vb) compute the vertex normals (one thread per
 // vertex, as k_vertex_normals; vb = 0 when the caller passed them), the rest zero `nzero` ints
@@ -1171,8 +1146,8 @@ static int launch_shade_render(const FwdParams& P, int64_t slots_cap, hipStream_
   static int g0 = 0, g1 = 0;
   if (!g0) g0 = resident_grid(k_shade_render<CH, 0>, 256, 4);
   if (!g1) g1 = resident_grid(k_shade_render<CH, 1>, 256, 4);
-  const bool spec = CH == 3 && P.S.tex_kind == 2 && P.S.tex8 && P.S.light_kind == 0 && !P.S.zbuf_mode &&
-                    !P.p2f32 && P.out_flags == (MR_OUT_DEPTH | MR_OUT_SIL | MR_OUT_RGB);
+  const bool spec = drop_in_shading(P.S, CH, P.out_flags) && !P.p2f32 &&
+                    P.out_flags == (MR_OUT_DEPTH | MR_OUT_SIL | MR_OUT_RGB);
   const int sg = shade_grid(slots_cap, spec ? g1 : g0);
   if (spec) MR_TIMED(KID_SHADE_RENDER, st, (k_shade_render<CH, 1><<<sg, 256, 0, st>>>(P)));
   else MR_TIMED(KID_SHADE_RENDER, st, (k_shade_render<CH, 0><<<sg, 256, 0, st>>>(P)));

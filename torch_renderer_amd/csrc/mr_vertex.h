@@ -5,18 +5,6 @@
 // ---------------------------------------------------------------------------
 // 4. vertex kernels (CSR adjacency, entries (face << 2 | corner) sorted by (corner, face))
 // ---------------------------------------------------------------------------
-MR_DEV void face_normal(const float* verts, const int32_t* faces, int f, float nf[3]) {
-  const int32_t i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-  float a[3], b[3];
-  for (int k = 0; k < 3; ++k) {
-    a[k] = verts[3 * i2 + k] - verts[3 * i1 + k];
-    b[k] = verts[3 * i0 + k] - verts[3 * i1 + k];
-  }
-  nf[0] = a[1] * b[2] - a[2] * b[1];
-  nf[1] = a[2] * b[0] - a[0] * b[2];
-  nf[2] = a[0] * b[1] - a[1] * b[0];
-}
-
 __global__ void __launch_bounds__(256) k_vertex_normals(const float* __restrict__ verts, int64_t V,
                                                         const int32_t* __restrict__ faces,
                                                         const int32_t* __restrict__ ptr, const int32_t* __restrict__ adj,
@@ -24,27 +12,6 @@ __global__ void __launch_bounds__(256) k_vertex_normals(const float* __restrict_
   const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (v < V) vertex_normal(verts, faces, ptr, adj, v, vn, vraw);
 }
-// verts_normals_packed for vertex v: the sum of its faces' (unnormalised) normals in CSR order
-// (the reference's index_add order), then F.normalize.
-MR_DEV void vertex_normal(const float* __restrict__ verts, const int32_t* __restrict__ faces,
-                          const int32_t* __restrict__ ptr, const int32_t* __restrict__ adj, int64_t v,
-                          float* __restrict__ vn, float* __restrict__ vraw) {
-  float s[3] = {0.f, 0.f, 0.f};
-  for (int e = ptr[v]; e < ptr[v + 1]; ++e) {
-    float nf[3];
-    face_normal(verts, faces, adj[e] >> 2, nf);
-    s[0] += nf[0];
-    s[1] += nf[1];
-    s[2] += nf[2];
-  }
-  float y[3], nrm, den;
-  normalize3(s, y, nrm, den);
-  for (int k = 0; k < 3; ++k) {
-    vn[3 * v + k] = y[k];
-    vraw[3 * v + k] = s[k];
-  }
-}
-
 // A: gNu[v] = normalize_bwd(raw[v], sum of the face totals' normal rows)
 // (face totals: fixed-point gfix + float gface on the fused path, gfix NULL: float gface alone)
 #define MR_VL 8  // lanes per vertex in the CSR gathers of the vertex-gradient kernels
