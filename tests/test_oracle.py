@@ -239,6 +239,56 @@ def test_cull_backfaces_equals_rasterizing_the_front_faces_only(K, blur, clip, f
         assert torch.equal(a.view(torch.int32), b.view(torch.int32)), f"{nm} not bitwise"
 
 
+def _bilinear_np(tex, u, v):
+    """TexturesUV sampling from its definition, float64 NumPy, no torch: position u (Wt - 1) along the
+    columns and (1 - v) (Ht - 1) along the rows of the map as stored (row 0 at v = 1), clamped to the map
+    (padding 'border'), the four surrounding texels weighted by the fractional parts."""
+    Ht, Wt = tex.shape[:2]
+    x = np.clip(u * (Wt - 1), 0.0, Wt - 1.0)
+    y = np.clip((1.0 - v) * (Ht - 1), 0.0, Ht - 1.0)
+    x0, y0 = np.floor(x).astype(np.int64), np.floor(y).astype(np.int64)
+    x1, y1 = np.minimum(x0 + 1, Wt - 1), np.minimum(y0 + 1, Ht - 1)
+    fx, fy = (x - x0)[:, None], (y - y0)[:, None]
+    return ((tex[y0, x0] * (1 - fx) + tex[y0, x1] * fx) * (1 - fy) + (tex[y1, x0] * (1 - fx) + tex[y1, x1] * fx) * fy)
+
+
+def _sample_oracle_at(tex, u, v):
+    """O.sample_textures_uv (float64) at the points (u, v): one face with corner uvs (0, 0), (1, 0), (0, 1),
+    so the barycentrics (1 - u - v, u, v) interpolate to (u, v) exactly (they may be negative: the sampler
+    does not care)."""
+    n = u.shape[0]
+    bary = torch.from_numpy(np.stack([1.0 - u - v, u, v], -1)).view(1, 1, n, 1, 3)
+    p2f = torch.zeros((1, 1, n, 1), dtype=torch.int64)
+    vuv = torch.tensor([[0.0, 0.0], [1.0, 0.0], [0.0, 1.0]], dtype=torch.float64)
+    out = O.sample_textures_uv(p2f, bary, vuv, torch.tensor([[0, 1, 2]]), torch.from_numpy(tex))
+    return out.view(n, tex.shape[-1]).numpy()
+
+
+@pytest.mark.parametrize("Ht,Wt", [(5, 7), (1, 6), (6, 1), (1, 1)])
+def test_sample_textures_uv_matches_the_definition(Ht, Wt):
+    """The oracle's sampler (torch.flip + F.grid_sample) against _bilinear_np at 200 random uvs in
+    [-0.5, 1.5]^2 (about half of them clamp on some axis), float64 on O(1) values: 1e-12. A random map and
+    one whose texels hold their own (row, col): a transposed or unflipped read is off by a whole texel."""
+    rng = np.random.default_rng(100 * Ht + Wt)
+    uv = rng.uniform(-0.5, 1.5, size=(200, 2))
+    u, v = uv[:, 0].copy(), uv[:, 1].copy()
+    outside = (uv < 0).any(1) | (uv > 1).any(1)
+    assert 50 <= int(outside.sum()) <= 190
+    rows, cols = np.meshgrid(np.arange(Ht, dtype=np.float64), np.arange(Wt, dtype=np.float64), indexing="ij")
+    coded = np.stack([rows, cols, rows * Wt + cols], -1) / max(Ht * Wt - 1, 1)  # (Ht, Wt, 3) in [0, 1]
+    for name, tex in (("random", rng.uniform(size=(Ht, Wt, 3))), ("row-col", coded)):
+        got, want = _sample_oracle_at(tex, u, v), _bilinear_np(tex, u, v)
+        err = np.abs(got - want).max()
+        print(f"[sampler] ({Ht}, {Wt}) {name}: max |oracle - definition| = {err:.2e}")
+        assert err <= 1e-12, (name, err)
+    # at the texel centres themselves the row-col map returns its own (row, col): row 0 at v = 1
+    cu = cols.reshape(-1) / max(Wt - 1, 1)
+    cv = 1.0 - rows.reshape(-1) / max(Ht - 1, 1)
+    got = _sample_oracle_at(coded, cu, cv) * max(Ht * Wt - 1, 1)
+    assert np.abs(got[:, 0] - rows.reshape(-1)).max() <= 1e-12 * max(Ht * Wt, 1)
+    assert np.abs(got[:, 1] - cols.reshape(-1)).max() <= 1e-12 * max(Ht * Wt, 1)
+
+
 def test_oracle_under_address_and_ub_sanitizers():
     """the C restatement built with -fsanitize=address,undefined and driven through
     every entry point (forward, neighbour rule, pair mode, window, K > 1, blur, backward,
