@@ -425,6 +425,54 @@ int32_t mr_mesh_priors_backward(const float* verts, int64_t V, const int32_t* nb
                                 int64_t P, float target_length, int32_t terms, const float* g_edge, const float* g_lap,
                                 const float* g_norm, const void* fwd_ws, float* grad_verts, void* stream);
 
+/* Point clouds (PyTorch3D chamfer_distance with its K = 1 nearest neighbours; mesh_deformer.py:299-352,
+ * deform_mesh_from_pcd.py:160-212, chamfer_loss_evaluation.py:126). x (N,P1,3), y (N,P2,3) float32 on the device;
+ * x_lengths / y_lengths (N) int64 device arrays or NULL (every cloud full; values are clamped to [0, P]).
+ * The distance is float32 in a fixed order without FMA: norm 2 (dx*dx + dy*dy) + dz*dz, norm 1 (|dx| + |dy|) + |dz|;
+ * equal distances resolve to the lowest target index. mr_nearest_points writes, for every point of x its nearest
+ * point of y (dist_x, idx_x (N,P1)) and the reverse (dist_y, idx_y (N,P2)); entries past a length, or of a cloud
+ * whose counterpart has length 0, are 0 / -1. Coordinates must be finite.
+ *
+ * mr_chamfer_forward: out = the loss ((N) floats without a batch-reduction flag, else 1 float): per cloud
+ * weights[n] * (sum of its points' distances, divided by max(length, 1) with MR_CHAMFER_POINT_MEAN), x -> y plus
+ * y -> x (x -> y alone with MR_CHAMFER_SINGLE); summed over the batch with MR_CHAMFER_BATCH_SUM, and divided by
+ * sum(weights) (N without weights; the loss is 0 when that sum is 0) with MR_CHAMFER_BATCH_MEAN. weights (N) may be
+ * NULL. idx_x / idx_y (may be NULL) and coef (2,N; may be NULL) are what the backward reads. All sums run in a fixed
+ * order; nothing is read back by the host. mr_chamfer_backward writes grad_x (N,P1,3) and grad_y (N,P2,3) for the
+ * upstream gradient grad_out (device: (N) without a batch-reduction flag, else 1 float); the many-to-one part is
+ * summed with 64-bit fixed-point integer atomics, so the result is bitwise reproducible (differences of
+ * magnitude >= 2^24 take float atomics). norm and flags must be those of the forward. The *_workspace queries
+ * return 0 when a size is out of range. */
+enum { MR_CHAMFER_POINT_MEAN = 1, MR_CHAMFER_BATCH_MEAN = 2, MR_CHAMFER_BATCH_SUM = 4, MR_CHAMFER_SINGLE = 8,
+       MR_CHAMFER_ALL = 15 };
+size_t mr_nearest_points_workspace(int64_t N, int64_t P1, int64_t P2);
+int32_t mr_nearest_points(const float* x, const float* y, int64_t N, int64_t P1, int64_t P2, const int64_t* x_lengths,
+                          const int64_t* y_lengths, int32_t norm, float* dist_x, int32_t* idx_x, float* dist_y,
+                          int32_t* idx_y, void* ws, size_t ws_bytes, void* stream);
+size_t mr_chamfer_workspace(int64_t N, int64_t P1, int64_t P2);
+int32_t mr_chamfer_forward(const float* x, const float* y, int64_t N, int64_t P1, int64_t P2, const int64_t* x_lengths,
+                           const int64_t* y_lengths, const float* weights, int32_t norm, int32_t flags, int32_t* idx_x,
+                           int32_t* idx_y, float* coef, float* out, void* ws, size_t ws_bytes, void* stream);
+size_t mr_chamfer_backward_workspace(int64_t N, int64_t P1, int64_t P2);
+int32_t mr_chamfer_backward(const float* x, const float* y, int64_t N, int64_t P1, int64_t P2, int32_t norm,
+                            int32_t flags, const int32_t* idx_x, const int32_t* idx_y, const float* coef,
+                            const float* grad_out, float* grad_x, float* grad_y, void* ws, size_t ws_bytes,
+                            void* stream);
+
+/* Points on the faces of a packed batch of meshes (PyTorch3D sample_points_from_meshes after its random draws):
+ * verts (V,3), faces (F,3) int32 over packed vertex ids, face_idx (M) packed face ids, uv (2,M) in [0,1).
+ * points[m] = (w0 a + w1 b) + w2 c with s = sqrt(u), w0 = 1 - s, w1 = s (1 - v), w2 = s v over face face_idx[m]'s
+ * corners a, b, c; zeros for a negative id (a mesh without faces). The backward sums w_k * grad_points[m] into the
+ * three vertices (grad_verts (V,3)) with the fixed-point atomics of mr_chamfer_backward (bitwise reproducible;
+ * resolution 2^-32 absolute). mr_face_areas: areas[f] = 0.5 |(b - a) x (c - a)|. */
+int32_t mr_sample_points_forward(const float* verts, int64_t V, const int32_t* faces, int64_t F,
+                                 const int32_t* face_idx, const float* uv, int64_t M, float* points, void* stream);
+size_t mr_sample_points_backward_workspace(int64_t V);
+int32_t mr_sample_points_backward(int64_t V, const int32_t* faces, int64_t F, const int32_t* face_idx, const float* uv,
+                                  int64_t M, const float* grad_points, float* grad_verts, void* ws, size_t ws_bytes,
+                                  void* stream);
+int32_t mr_face_areas(const float* verts, int64_t V, const int32_t* faces, int64_t F, float* areas, void* stream);
+
 /* Work counters left in `workspace` by the last mr_render_forward / mr_rasterize_meshes that used it
  * (same N, total faces, H, W, max_faces_per_bin). Synchronises `stream`; for benchmarks and tools.
  * out[0] = (tile, face) list entries, out[1] = raster work units, out[2] = non-empty 8x8 tiles,

@@ -30,6 +30,7 @@ MR_SREC_SLOT_SHIFT = 8  # out_flags bits 8-9: the workspace's ShadeRec slot (mr_
 MR_FRAG_SORTED = 1024  # mr_shade_fragments_*: empty slots follow the filled ones (this library's rasterizer)
 MR_GRAD_ROWS_CLEARED = 16  # mr_render_backward: first backward over a forward (its face totals are still clear)
 MR_PRIOR_EDGE, MR_PRIOR_LAPLACIAN, MR_PRIOR_NORMAL, MR_PRIOR_ALL = 1, 2, 4, 7  # mr_mesh_priors_*: terms mask
+MR_CHAMFER_POINT_MEAN, MR_CHAMFER_BATCH_MEAN, MR_CHAMFER_BATCH_SUM, MR_CHAMFER_SINGLE = 1, 2, 4, 8  # mr_chamfer_*: flags
 
 
 class MrView(ctypes.Structure):
@@ -149,6 +150,18 @@ _SIGS = [
                                       _I32, _VP, _VP, _SZ, _VP]),
     ("mr_mesh_priors_backward", _I32, [_VP, _I64, _VP, _VP, _VP, _VP, _VP, _I64, _I64, ctypes.c_float, _I32, _VP,
                                        _VP, _VP, _VP, _VP, _VP]),
+    ("mr_nearest_points_workspace", _SZ, [_I64, _I64, _I64]),
+    ("mr_nearest_points", _I32, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    ("mr_chamfer_workspace", _SZ, [_I64, _I64, _I64]),
+    ("mr_chamfer_forward", _I32, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _SZ,
+                                  _VP]),
+    ("mr_chamfer_backward_workspace", _SZ, [_I64, _I64, _I64]),
+    ("mr_chamfer_backward", _I32, [_VP, _VP, _I64, _I64, _I64, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ,
+                                   _VP]),
+    ("mr_sample_points_forward", _I32, [_VP, _I64, _VP, _I64, _VP, _VP, _I64, _VP, _VP]),
+    ("mr_sample_points_backward_workspace", _SZ, [_I64]),
+    ("mr_sample_points_backward", _I32, [_I64, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _SZ, _VP]),
+    ("mr_face_areas", _I32, [_VP, _I64, _VP, _I64, _VP, _VP]),
     ("mr_workspace_stats", _I32, [_VP, _I64, _I64, _I32, _I32, _I32, _VP, _VP]),
     ("mr_workspace_counters", _I32, [_VP, _I64, _I64, _I32, _I32, _I32, _VP, _VP]),
     ("mr_per_view_binning", _I32, [_I64, _I64, _I32, _I32]),

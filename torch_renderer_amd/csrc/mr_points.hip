@@ -1,0 +1,600 @@
+// mi355r — point-cloud losses and mesh sampling (PyTorch3D chamfer_distance with K = 1 nearest neighbours,
+// sample_points_from_meshes' point construction, face areas): mr_nearest_points / mr_chamfer_* /
+// mr_sample_points_* / mr_face_areas of include/mi355r.h. A translation unit of its own (the render kernels of
+// mr_raster.hip and the priors of mr_priors.hip are compiled as before).
+//
+//   k_nn            both directions (x -> y, y -> x) of a batch in one launch. A workgroup of 128 threads takes
+//                   512 queries (4 per thread, in registers) and one chunk of <= 1024 targets staged in LDS as
+//                   float4; every lane reads the same LDS address (a broadcast), one read feeds 4 distance
+//                   evaluations (44 VALU instructions: the loop is VALU-bound). The target range is split into chunks over workgroups (the host picks the chunk
+//                   so that ~1024 workgroups exist per direction); each thread merges its chunk's minimum with a
+//                   64-bit atomicMin on (float bits of dist) << 32 | target index: non-negative float bits order
+//                   as unsigned integers, the minimum does not depend on arrival order, and equal distances
+//                   resolve to the lowest index. The key buffer is set to all-ones by a memset ahead of the launch.
+//                   dist = (dx*dx + dy*dy) + dz*dz or (|dx| + |dy|) + |dz| in float32, no FMA.
+//   k_nn_reduce     keys -> dist (float32) / idx (int32) per point, 0 / -1 for entries past a length or of a cloud
+//                   whose counterpart is empty; per-workgroup partial sums of dist (double, fixed tree).
+//   k_cham_final    per cloud: sums the partials in order, applies weights and the point reduction; then the batch
+//                   reduction in a fixed order. Also leaves the backward's per-cloud coefficients.
+//   k_cham_scatter  backward, the many-to-one part: every query adds (q - t) (norm 2) or sign(q - t) (norm 1) to its
+//                   target's row with 64-bit fixed-point integer atomics (mr_common.h; addends >= MR_FIX_MAX go to
+//                   a float remainder row). The rows hold UNSCALED differences: the coefficients are applied after.
+//   k_cham_grad     backward: grad = k (c_own (p - nn(p)) - c_other row(p)), k = 2 or 1, one store per entry.
+//   k_sample_fwd / k_sample_scatter / k_fix_to_float, k_face_areas: see the entry points below.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "../../include/mi355r.h"
+#include "mr_common.h"
+
+extern "C" int mr_set_error_(int code, const char* msg);  // mr_raster.hip: the library's thread-local error text
+
+#define MRN_BLOCK 128                  // threads of a k_nn workgroup (two waves)
+#define MRN_Q 4                        // queries per thread
+#define MRN_QT (MRN_BLOCK * MRN_Q)     // queries per workgroup
+#define MRN_MAXCHUNK 1024              // targets staged per workgroup at most (16 KiB of LDS)
+#define MRN_MINCHUNK 64
+#define MRN_WANT_GROUPS 1024           // workgroups per direction the chunk size aims for
+#define MRR_BLOCK 256                  // threads of the other kernels
+#define MRR_PER 4                      // points per thread of k_nn_reduce
+#define MRR_TILE (MRR_BLOCK * MRR_PER)
+
+namespace {
+
+typedef unsigned long long u64;
+
+struct NNGeom {
+  int64_t N, P[2];     // clouds; points of x and of y (padded)
+  int chunk[2];        // targets per workgroup of direction d (d = 0: queries x, targets y)
+  int64_t nchunk[2];   // chunks of direction d
+  int64_t groups[2];   // workgroups of direction d per cloud
+};
+
+inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
+
+bool sizes_ok(int64_t N, int64_t P1, int64_t P2) {
+  // per-cloud indices are int32; the grid's y dimension is the batch
+  return N >= 1 && P1 >= 1 && P2 >= 1 && N <= 65535 && P1 < 0x7fffffffll && P2 < 0x7fffffffll &&
+         N * P1 < (1ll << 40) / 3 && N * P2 < (1ll << 40) / 3;
+}
+
+NNGeom nn_geom(int64_t N, int64_t P1, int64_t P2) {
+  NNGeom g;
+  g.N = N;
+  g.P[0] = P1;
+  g.P[1] = P2;
+  for (int d = 0; d < 2; ++d) {
+    const int64_t Pq = g.P[d], Pt = g.P[1 - d];
+    const int64_t qtiles = (Pq + MRN_QT - 1) / MRN_QT;
+    int64_t want = MRN_WANT_GROUPS / (N * qtiles);
+    if (want < 1) want = 1;
+    int64_t c = ((Pt + want - 1) / want + 63) / 64 * 64;
+    if (c < MRN_MINCHUNK) c = MRN_MINCHUNK;
+    if (c > MRN_MAXCHUNK) c = MRN_MAXCHUNK;
+    g.chunk[d] = (int)c;
+    g.nchunk[d] = (Pt + c - 1) / c;
+    g.groups[d] = qtiles * g.nchunk[d];
+  }
+  return g;
+}
+
+struct PointsWS {
+  u64* key[2];    // (N, P1), (N, P2)
+  double* part;   // (2, N, nblk)
+  int64_t nblk;
+  size_t key_bytes, bytes;
+};
+PointsWS carve_points(void* base, int64_t N, int64_t P1, int64_t P2) {
+  PointsWS w;
+  char* b = (char*)base;
+  size_t off = 0;
+  w.key[0] = (u64*)(b + off);
+  off += sizeof(u64) * (size_t)(N * P1);
+  w.key[1] = (u64*)(b + off);
+  off += sizeof(u64) * (size_t)(N * P2);
+  w.key_bytes = off;
+  off = align256(off);
+  const int64_t pm = P1 > P2 ? P1 : P2;
+  w.nblk = (pm + MRR_TILE - 1) / MRR_TILE;
+  w.part = (double*)(b + off);
+  off = align256(off + sizeof(double) * 2 * (size_t)(N * w.nblk));
+  w.bytes = off;
+  return w;
+}
+
+// Fixed-point rows of a scatter's targets: `n` 64-bit words, then `n` float remainders.
+struct FixWS {
+  u64* fix;
+  float* rem;
+  size_t bytes;
+};
+FixWS carve_fix(void* base, int64_t n) {
+  FixWS w;
+  w.fix = (u64*)base;
+  w.rem = (float*)((char*)base + sizeof(u64) * (size_t)n);
+  w.bytes = align256((sizeof(u64) + sizeof(float)) * (size_t)n);
+  return w;
+}
+
+__device__ __forceinline__ int64_t cloud_len(const int64_t* __restrict__ lengths, int64_t n, int64_t P) {
+  if (!lengths) return P;
+  const int64_t l = lengths[n];
+  return l < 0 ? 0 : (l > P ? P : l);
+}
+
+template <int NORM> __device__ __forceinline__ float dist3(float qx, float qy, float qz, float4 t) {
+  const float dx = qx - t.x, dy = qy - t.y, dz = qz - t.z;
+  if (NORM == 2) return (dx * dx + dy * dy) + dz * dz;
+  return (fabsf(dx) + fabsf(dy)) + fabsf(dz);
+}
+
+template <int NORM>
+__global__ void __launch_bounds__(MRN_BLOCK) k_nn(const float* __restrict__ x, const float* __restrict__ y, NNGeom g,
+                                                  const int64_t* __restrict__ xl, const int64_t* __restrict__ yl,
+                                                  u64* __restrict__ key_x, u64* __restrict__ key_y) {
+  __shared__ float4 sm[MRN_MAXCHUNK];
+  const int d = blockIdx.z;
+  if ((int64_t)blockIdx.x >= g.groups[d]) return;
+  const int64_t n = blockIdx.y;
+  const int64_t Pq = g.P[d], Pt = g.P[1 - d];
+  const float* __restrict__ q = (d ? y : x) + 3 * n * Pq;
+  const float* __restrict__ t = (d ? x : y) + 3 * n * Pt;
+  const int64_t lq = cloud_len(d ? yl : xl, n, Pq), lt = cloud_len(d ? xl : yl, n, Pt);
+  const int64_t q0 = ((int64_t)blockIdx.x / g.nchunk[d]) * MRN_QT;
+  const int64_t t0 = ((int64_t)blockIdx.x % g.nchunk[d]) * g.chunk[d];
+  if (q0 >= lq || t0 >= lt) return;  // uniform over the workgroup
+  const int cnt = (int)((lt - t0 < g.chunk[d]) ? lt - t0 : g.chunk[d]);
+  for (int j = threadIdx.x; j < cnt; j += MRN_BLOCK) {
+    const float* p = t + 3 * (t0 + j);
+    sm[j] = make_float4(p[0], p[1], p[2], 0.0f);
+  }
+  __syncthreads();
+
+  float qx[MRN_Q], qy[MRN_Q], qz[MRN_Q], best[MRN_Q];
+  int bi[MRN_Q];
+#pragma unroll
+  for (int k = 0; k < MRN_Q; ++k) {
+    const int64_t i = q0 + k * MRN_BLOCK + threadIdx.x;
+    const bool ok = i < lq;
+    qx[k] = ok ? q[3 * i] : 0.0f;
+    qy[k] = ok ? q[3 * i + 1] : 0.0f;
+    qz[k] = ok ? q[3 * i + 2] : 0.0f;
+    best[k] = __builtin_inff();
+    bi[k] = 0;
+  }
+#pragma unroll 4
+  for (int j = 0; j < cnt; ++j) {
+    const float4 p = sm[j];
+#pragma unroll
+    for (int k = 0; k < MRN_Q; ++k) {
+      const float dd = dist3<NORM>(qx[k], qy[k], qz[k], p);
+      if (dd < best[k]) {  // strict: the lowest index wins a tie inside the chunk
+        best[k] = dd;
+        bi[k] = j;
+      }
+    }
+  }
+  u64* __restrict__ key = (d ? key_y : key_x) + n * Pq;
+#pragma unroll
+  for (int k = 0; k < MRN_Q; ++k) {
+    const int64_t i = q0 + k * MRN_BLOCK + threadIdx.x;
+    if (i < lq) atomicMin(&key[i], ((u64)__float_as_uint(best[k]) << 32) | (u64)(uint32_t)(t0 + bi[k]));
+  }
+}
+
+// Sum over the workgroup in a fixed tree (xor butterflies inside each wave, then the four waves in order).
+__device__ __forceinline__ double block_sum(double v, double* sm) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const double t = ((sm[0] + sm[1]) + sm[2]) + sm[3];
+  __syncthreads();
+  return t;
+}
+
+// grid (nblk, N, directions). dist / idx / part may each be NULL.
+__global__ void __launch_bounds__(MRR_BLOCK) k_nn_reduce(NNGeom g, const int64_t* __restrict__ xl,
+                                                         const int64_t* __restrict__ yl, const u64* __restrict__ key_x,
+                                                         const u64* __restrict__ key_y, float* __restrict__ dist_x,
+                                                         int32_t* __restrict__ idx_x, float* __restrict__ dist_y,
+                                                         int32_t* __restrict__ idx_y, double* __restrict__ part,
+                                                         int64_t nblk) {
+  __shared__ double sm[4];
+  const int d = blockIdx.z;
+  const int64_t n = blockIdx.y;
+  const int64_t Pq = g.P[d], Pt = g.P[1 - d];
+  const int64_t lq = cloud_len(d ? yl : xl, n, Pq), lt = cloud_len(d ? xl : yl, n, Pt);
+  const u64* __restrict__ key = (d ? key_y : key_x) + n * Pq;
+  float* __restrict__ dist = d ? dist_y : dist_x;
+  int32_t* __restrict__ idx = d ? idx_y : idx_x;
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < MRR_PER; ++k) {
+    const int64_t i = (int64_t)blockIdx.x * MRR_TILE + k * MRR_BLOCK + threadIdx.x;
+    if (i >= Pq) continue;
+    const bool ok = i < lq && lt > 0;
+    const u64 kk = ok ? key[i] : 0;
+    const float dv = ok ? __uint_as_float((uint32_t)(kk >> 32)) : 0.0f;
+    if (dist) dist[n * Pq + i] = dv;
+    if (idx) idx[n * Pq + i] = ok ? (int32_t)(uint32_t)kk : -1;
+    s += (double)dv;
+  }
+  if (part) {  // uniform
+    s = block_sum(s, sm);
+    if (threadIdx.x == 0) part[((int64_t)d * g.N + n) * nblk + blockIdx.x] = s;
+  }
+}
+
+// One workgroup. Thread t takes clouds t, t + 256, ...: each cloud's partials are summed in order; out[n] for
+// batch_reduction None, else the clouds' values are summed per thread in order and then in the fixed tree.
+// coef (2, N): d loss / d (cloud n's point sum of direction d) for an upstream gradient of 1.
+__global__ void __launch_bounds__(MRR_BLOCK) k_cham_final(const double* __restrict__ part, int64_t nblk, int64_t N,
+                                                          int64_t P1, int64_t P2, const int64_t* __restrict__ xl,
+                                                          const int64_t* __restrict__ yl,
+                                                          const float* __restrict__ weights, int flags,
+                                                          float* __restrict__ out, float* __restrict__ coef) {
+  __shared__ double sm[4];
+  const bool single = flags & MR_CHAMFER_SINGLE, pmean = flags & MR_CHAMFER_POINT_MEAN;
+  double wsum = 0.0;
+  for (int64_t n = threadIdx.x; n < N; n += MRR_BLOCK) wsum += weights ? (double)weights[n] : 1.0;
+  wsum = block_sum(wsum, sm);
+  double scale = 1.0;  // of the batch reduction
+  if (flags & MR_CHAMFER_BATCH_MEAN) {
+    const double div = weights ? wsum : (double)(N > 1 ? N : 1);
+    scale = div != 0.0 ? 1.0 / div : 0.0;
+  }
+  const bool per_cloud = !(flags & (MR_CHAMFER_BATCH_MEAN | MR_CHAMFER_BATCH_SUM));
+  double total = 0.0;
+  for (int64_t n = threadIdx.x; n < N; n += MRR_BLOCK) {
+    const int64_t lx = cloud_len(xl, n, P1), ly = cloud_len(yl, n, P2);
+    const double w = weights ? (double)weights[n] : 1.0;
+    double v = 0.0;
+    for (int d = 0; d < (single ? 1 : 2); ++d) {
+      const int64_t lq = d ? ly : lx, lt = d ? lx : ly;
+      const double c = w * (pmean ? 1.0 / (double)(lq > 1 ? lq : 1) : 1.0);
+      double s = 0.0;
+      for (int64_t b = 0; b < nblk; ++b) s += part[((int64_t)d * N + n) * nblk + b];
+      v += c * s;
+      if (coef) coef[(int64_t)d * N + n] = lt > 0 ? (float)(c * scale) : 0.0f;
+    }
+    if (single && coef) coef[N + n] = 0.0f;
+    if (per_cloud) out[n] = (float)v;
+    total += v;
+  }
+  total = block_sum(total, sm);
+  if (!per_cloud && threadIdx.x == 0) out[0] = (float)(total * scale);
+}
+
+// Adds v to fixed-point word i (or to the float remainder when |v| >= MR_FIX_MAX; non-finite addends too).
+__device__ __forceinline__ void fix_add(u64* __restrict__ fix, float* __restrict__ rem, int64_t i, float v) {
+  if (v == 0.0f) return;
+  if (fabsf(v) < MR_FIX_MAX) atomicAdd(&fix[i], (u64)fix_of(v));
+  else atomicAdd(&rem[i], v);
+}
+
+__device__ __forceinline__ float sgn(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }
+
+// grid (blocks over max(P1, P2), N, directions): point i of direction d's queries adds its difference to its
+// target's row. fix / rem: (N, P1, 3) rows of x then (N, P2, 3) rows of y.
+template <int NORM>
+__global__ void __launch_bounds__(MRR_BLOCK) k_cham_scatter(const float* __restrict__ x, const float* __restrict__ y,
+                                                            int64_t N, int64_t P1, int64_t P2,
+                                                            const int32_t* __restrict__ idx_x,
+                                                            const int32_t* __restrict__ idx_y, u64* __restrict__ fix,
+                                                            float* __restrict__ rem) {
+  const int d = blockIdx.z;
+  const int64_t n = blockIdx.y;
+  const int64_t Pq = d ? P2 : P1, Pt = d ? P1 : P2;
+  const int64_t i = (int64_t)blockIdx.x * MRR_BLOCK + threadIdx.x;
+  if (i >= Pq) return;
+  const int32_t j = (d ? idx_y : idx_x)[n * Pq + i];
+  if (j < 0 || j >= Pt) return;
+  const float* __restrict__ q = (d ? y : x) + 3 * (n * Pq + i);
+  const float* __restrict__ t = (d ? x : y) + 3 * (n * Pt + j);
+  const int64_t row = 3 * ((d ? 0 : N * P1) + n * Pt + j);  // the target's row
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float df = q[c] - t[c];
+    fix_add(fix, rem, row + c, NORM == 2 ? df : sgn(df));
+  }
+}
+
+template <int NORM>
+__global__ void __launch_bounds__(MRR_BLOCK) k_cham_grad(const float* __restrict__ x, const float* __restrict__ y,
+                                                         int64_t N, int64_t P1, int64_t P2,
+                                                         const int32_t* __restrict__ idx_x,
+                                                         const int32_t* __restrict__ idx_y,
+                                                         const float* __restrict__ coef, const float* __restrict__ g,
+                                                         int g_per_cloud, const u64* __restrict__ fix,
+                                                         const float* __restrict__ rem, float* __restrict__ grad_x,
+                                                         float* __restrict__ grad_y) {
+  const int d = blockIdx.z;
+  const int64_t n = blockIdx.y;
+  const int64_t Pq = d ? P2 : P1, Pt = d ? P1 : P2;
+  const int64_t i = (int64_t)blockIdx.x * MRR_BLOCK + threadIdx.x;
+  if (i >= Pq) return;
+  const float up = g_per_cloud ? g[n] : g[0];
+  const float k = NORM == 2 ? 2.0f : 1.0f;
+  const float c_own = k * up * coef[(int64_t)d * N + n], c_other = k * up * coef[(int64_t)(1 - d) * N + n];
+  const int32_t* __restrict__ idx = d ? idx_y : idx_x;
+  const int32_t j = idx ? idx[n * Pq + i] : -1;
+  const bool has = j >= 0 && j < Pt;
+  const float* __restrict__ q = (d ? y : x) + 3 * (n * Pq + i);
+  const float* __restrict__ t = (d ? x : y) + 3 * (n * Pt + (has ? j : 0));
+  const int64_t row = 3 * ((d ? N * P1 : 0) + n * Pq + i);  // this point's own row
+  float* __restrict__ out = (d ? grad_y : grad_x) + 3 * (n * Pq + i);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float own = 0.0f;
+    if (has) {
+      const float df = q[c] - t[c];
+      own = NORM == 2 ? df : sgn(df);
+    }
+    const float other = fix_to_f(fix[row + c]) + rem[row + c];
+    out[c] = c_own * own - c_other * other;
+  }
+}
+
+__device__ __forceinline__ bool face_ok(const int32_t* __restrict__ faces, int64_t F, int64_t V, int64_t f, int& a,
+                                        int& b, int& c) {
+  if (f < 0 || f >= F) return false;
+  a = faces[3 * f];
+  b = faces[3 * f + 1];
+  c = faces[3 * f + 2];
+  return a >= 0 && b >= 0 && c >= 0 && a < V && b < V && c < V;
+}
+
+__device__ __forceinline__ void bary_of(float u, float v, float& w0, float& w1, float& w2) {
+  const float s = sqrtf(u);
+  w0 = 1.0f - s;
+  w1 = s * (1.0f - v);
+  w2 = s * v;
+}
+
+// Sample m (of M = N * S): p = (w0 a + w1 b) + w2 c of face face_idx[m]; zeros for a negative (or out-of-range) id.
+__global__ void __launch_bounds__(MRR_BLOCK) k_sample_fwd(const float* __restrict__ verts, int64_t V,
+                                                          const int32_t* __restrict__ faces, int64_t F,
+                                                          const int32_t* __restrict__ face_idx,
+                                                          const float* __restrict__ uv, int64_t M,
+                                                          float* __restrict__ out) {
+  const int64_t m = (int64_t)blockIdx.x * MRR_BLOCK + threadIdx.x;
+  if (m >= M) return;
+  int a, b, c;
+  float p[3] = {0.0f, 0.0f, 0.0f};
+  if (face_ok(faces, F, V, face_idx[m], a, b, c)) {
+    float w0, w1, w2;
+    bary_of(uv[m], uv[M + m], w0, w1, w2);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[k] = (w0 * verts[3 * (int64_t)a + k] + w1 * verts[3 * (int64_t)b + k]) + w2 * verts[3 * (int64_t)c + k];
+  }
+  out[3 * m] = p[0];
+  out[3 * m + 1] = p[1];
+  out[3 * m + 2] = p[2];
+}
+
+__global__ void __launch_bounds__(MRR_BLOCK) k_sample_scatter(int64_t V, const int32_t* __restrict__ faces, int64_t F,
+                                                              const int32_t* __restrict__ face_idx,
+                                                              const float* __restrict__ uv, int64_t M,
+                                                              const float* __restrict__ gp, u64* __restrict__ fix,
+                                                              float* __restrict__ rem) {
+  const int64_t m = (int64_t)blockIdx.x * MRR_BLOCK + threadIdx.x;
+  if (m >= M) return;
+  int a, b, c;
+  if (!face_ok(faces, F, V, face_idx[m], a, b, c)) return;
+  float w0, w1, w2;
+  bary_of(uv[m], uv[M + m], w0, w1, w2);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float gk = gp[3 * m + k];
+    fix_add(fix, rem, 3 * (int64_t)a + k, w0 * gk);
+    fix_add(fix, rem, 3 * (int64_t)b + k, w1 * gk);
+    fix_add(fix, rem, 3 * (int64_t)c + k, w2 * gk);
+  }
+}
+
+__global__ void __launch_bounds__(MRR_BLOCK) k_fix_to_float(const u64* __restrict__ fix, const float* __restrict__ rem,
+                                                            int64_t n, float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * MRR_BLOCK + threadIdx.x;
+  if (i < n) out[i] = fix_to_f(fix[i]) + rem[i];
+}
+
+__global__ void __launch_bounds__(MRR_BLOCK) k_face_areas(const float* __restrict__ verts, int64_t V,
+                                                          const int32_t* __restrict__ faces, int64_t F,
+                                                          float* __restrict__ areas) {
+  const int64_t f = (int64_t)blockIdx.x * MRR_BLOCK + threadIdx.x;
+  if (f >= F) return;
+  int a, b, c;
+  float area = 0.0f;
+  if (face_ok(faces, F, V, f, a, b, c)) {
+    const float* pa = verts + 3 * (int64_t)a;
+    const float* pb = verts + 3 * (int64_t)b;
+    const float* pc = verts + 3 * (int64_t)c;
+    const float ux = pb[0] - pa[0], uy = pb[1] - pa[1], uz = pb[2] - pa[2];
+    const float vx = pc[0] - pa[0], vy = pc[1] - pa[1], vz = pc[2] - pa[2];
+    const float cx = uy * vz - uz * vy, cy = uz * vx - ux * vz, cz = ux * vy - uy * vx;
+    area = 0.5f * sqrtf((cx * cx + cy * cy) + cz * cz);
+  }
+  areas[f] = area;
+}
+
+int launch_error(const char* name) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return MR_OK;
+  char msg[256];
+  snprintf(msg, sizeof(msg), "%s: %s", name, hipGetErrorString(e));
+  return mr_set_error_(MR_ELAUNCH, msg);
+}
+
+inline unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
+int check_clouds(const char* who, const float* x, const float* y, int64_t N, int64_t P1, int64_t P2, int32_t norm) {
+  char msg[160];
+  if (N < 1 || P1 < 1 || P2 < 1) {
+    snprintf(msg, sizeof(msg), "%s: N, P1 and P2 must be >= 1", who);
+    return mr_set_error_(MR_EINVAL, msg);
+  }
+  if (!sizes_ok(N, P1, P2)) {
+    snprintf(msg, sizeof(msg), "%s: more than 65535 clouds or clouds too large for 32-bit point ids", who);
+    return mr_set_error_(MR_EUNSUPPORTED, msg);
+  }
+  if (norm != 1 && norm != 2) {
+    snprintf(msg, sizeof(msg), "%s: norm must be 1 or 2", who);
+    return mr_set_error_(MR_EINVAL, msg);
+  }
+  if (!x || !y) {
+    snprintf(msg, sizeof(msg), "%s: x / y is NULL", who);
+    return mr_set_error_(MR_EINVAL, msg);
+  }
+  return MR_OK;
+}
+
+// memset of the keys + k_nn for `dirs` directions.
+int run_nn(const float* x, const float* y, const NNGeom& g, const int64_t* xl, const int64_t* yl, int32_t norm, int dirs,
+           const PointsWS& w, hipStream_t st) {
+  if (g.groups[0] > 0x7fffffffll || g.groups[1] > 0x7fffffffll)
+    return mr_set_error_(MR_EUNSUPPORTED, "nearest points: P1 * P2 is too large for one launch");
+  if (hipMemsetAsync(w.key[0], 0xff, w.key_bytes, st) != hipSuccess) return launch_error("nearest points: memset");
+  const int64_t gx = (dirs == 2 && g.groups[1] > g.groups[0]) ? g.groups[1] : g.groups[0];
+  const dim3 grid((unsigned)gx, (unsigned)g.N, (unsigned)dirs);
+  if (norm == 2) hipLaunchKernelGGL(k_nn<2>, grid, dim3(MRN_BLOCK), 0, st, x, y, g, xl, yl, w.key[0], w.key[1]);
+  else hipLaunchKernelGGL(k_nn<1>, grid, dim3(MRN_BLOCK), 0, st, x, y, g, xl, yl, w.key[0], w.key[1]);
+  return launch_error("k_nn");
+}
+
+bool mesh_sizes_ok(int64_t V, int64_t F, int64_t M) {
+  return V >= 0 && F >= 0 && M >= 0 && V < 0x7fffffffll / 3 && F < 0x7fffffffll / 3 && M < (1ll << 31) * MRR_BLOCK / 4;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mr_nearest_points_workspace(int64_t N, int64_t P1, int64_t P2) {
+  if (!sizes_ok(N, P1, P2)) return 0;
+  return carve_points(nullptr, N, P1, P2).bytes;
+}
+
+int32_t mr_nearest_points(const float* x, const float* y, int64_t N, int64_t P1, int64_t P2, const int64_t* x_lengths,
+                          const int64_t* y_lengths, int32_t norm, float* dist_x, int32_t* idx_x, float* dist_y,
+                          int32_t* idx_y, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = check_clouds("nearest points", x, y, N, P1, P2, norm)) return rc;
+  if (!dist_x || !idx_x || !dist_y || !idx_y || !ws)
+    return mr_set_error_(MR_EINVAL, "nearest points: an output or the workspace is NULL");
+  const PointsWS w = carve_points(ws, N, P1, P2);
+  if (ws_bytes < w.bytes) return mr_set_error_(MR_EWORKSPACE, "nearest points workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  const NNGeom g = nn_geom(N, P1, P2);
+  if (int rc = run_nn(x, y, g, x_lengths, y_lengths, norm, 2, w, st)) return rc;
+  hipLaunchKernelGGL(k_nn_reduce, dim3((unsigned)w.nblk, (unsigned)N, 2), dim3(MRR_BLOCK), 0, st, g, x_lengths,
+                     y_lengths, w.key[0], w.key[1], dist_x, idx_x, dist_y, idx_y, (double*)nullptr, w.nblk);
+  return launch_error("k_nn_reduce");
+}
+
+size_t mr_chamfer_workspace(int64_t N, int64_t P1, int64_t P2) { return mr_nearest_points_workspace(N, P1, P2); }
+
+int32_t mr_chamfer_forward(const float* x, const float* y, int64_t N, int64_t P1, int64_t P2, const int64_t* x_lengths,
+                           const int64_t* y_lengths, const float* weights, int32_t norm, int32_t flags, int32_t* idx_x,
+                           int32_t* idx_y, float* coef, float* out, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = check_clouds("chamfer", x, y, N, P1, P2, norm)) return rc;
+  if ((flags & ~MR_CHAMFER_ALL) || ((flags & MR_CHAMFER_BATCH_MEAN) && (flags & MR_CHAMFER_BATCH_SUM)))
+    return mr_set_error_(MR_EINVAL, "chamfer: unknown or contradictory bits in flags");
+  if (!out || !ws) return mr_set_error_(MR_EINVAL, "chamfer: out / workspace is NULL");
+  const PointsWS w = carve_points(ws, N, P1, P2);
+  if (ws_bytes < w.bytes) return mr_set_error_(MR_EWORKSPACE, "chamfer workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  const int dirs = (flags & MR_CHAMFER_SINGLE) ? 1 : 2;
+  const NNGeom g = nn_geom(N, P1, P2);
+  if (int rc = run_nn(x, y, g, x_lengths, y_lengths, norm, dirs, w, st)) return rc;
+  hipLaunchKernelGGL(k_nn_reduce, dim3((unsigned)w.nblk, (unsigned)N, (unsigned)dirs), dim3(MRR_BLOCK), 0, st, g,
+                     x_lengths, y_lengths, w.key[0], w.key[1], (float*)nullptr, idx_x, (float*)nullptr, idx_y, w.part,
+                     w.nblk);
+  if (int rc = launch_error("k_nn_reduce")) return rc;
+  hipLaunchKernelGGL(k_cham_final, dim3(1), dim3(MRR_BLOCK), 0, st, w.part, w.nblk, N, P1, P2, x_lengths, y_lengths,
+                     weights, flags, out, coef);
+  return launch_error("k_cham_final");
+}
+
+size_t mr_chamfer_backward_workspace(int64_t N, int64_t P1, int64_t P2) {
+  if (!sizes_ok(N, P1, P2)) return 0;
+  return carve_fix(nullptr, 3 * N * (P1 + P2)).bytes;
+}
+
+int32_t mr_chamfer_backward(const float* x, const float* y, int64_t N, int64_t P1, int64_t P2, int32_t norm,
+                            int32_t flags, const int32_t* idx_x, const int32_t* idx_y, const float* coef,
+                            const float* grad_out, float* grad_x, float* grad_y, void* ws, size_t ws_bytes,
+                            void* stream) {
+  if (int rc = check_clouds("chamfer backward", x, y, N, P1, P2, norm)) return rc;
+  if (flags & ~MR_CHAMFER_ALL) return mr_set_error_(MR_EINVAL, "chamfer backward: unknown bits in flags");
+  const bool single = flags & MR_CHAMFER_SINGLE;
+  if (!idx_x || (!single && !idx_y) || !coef || !grad_out || !grad_x || !grad_y || !ws)
+    return mr_set_error_(MR_EINVAL, "chamfer backward: NULL pointer");
+  const FixWS w = carve_fix(ws, 3 * N * (P1 + P2));
+  if (ws_bytes < w.bytes) return mr_set_error_(MR_EWORKSPACE, "chamfer backward workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  if (single) idx_y = nullptr;
+  if (hipMemsetAsync(ws, 0, w.bytes, st) != hipSuccess) return launch_error("chamfer backward: memset");
+  const int per_cloud = !(flags & (MR_CHAMFER_BATCH_MEAN | MR_CHAMFER_BATCH_SUM));
+  const unsigned nb = blocks_of(P1 > P2 ? P1 : P2, MRR_BLOCK);
+  const dim3 gs(nb, (unsigned)N, single ? 1u : 2u), gg(nb, (unsigned)N, 2u), blk(MRR_BLOCK);
+  if (norm == 2) {
+    hipLaunchKernelGGL(k_cham_scatter<2>, gs, blk, 0, st, x, y, N, P1, P2, idx_x, idx_y, w.fix, w.rem);
+    if (int rc = launch_error("k_cham_scatter")) return rc;
+    hipLaunchKernelGGL(k_cham_grad<2>, gg, blk, 0, st, x, y, N, P1, P2, idx_x, idx_y, coef, grad_out, per_cloud,
+                       w.fix, w.rem, grad_x, grad_y);
+  } else {
+    hipLaunchKernelGGL(k_cham_scatter<1>, gs, blk, 0, st, x, y, N, P1, P2, idx_x, idx_y, w.fix, w.rem);
+    if (int rc = launch_error("k_cham_scatter")) return rc;
+    hipLaunchKernelGGL(k_cham_grad<1>, gg, blk, 0, st, x, y, N, P1, P2, idx_x, idx_y, coef, grad_out, per_cloud,
+                       w.fix, w.rem, grad_x, grad_y);
+  }
+  return launch_error("k_cham_grad");
+}
+
+int32_t mr_sample_points_forward(const float* verts, int64_t V, const int32_t* faces, int64_t F,
+                                 const int32_t* face_idx, const float* uv, int64_t M, float* points, void* stream) {
+  if (!mesh_sizes_ok(V, F, M)) return mr_set_error_(MR_EINVAL, "sample points: V, F or the sample count out of range");
+  if (M == 0) return MR_OK;
+  if (!face_idx || !uv || !points || (F > 0 && (!faces || !verts)))
+    return mr_set_error_(MR_EINVAL, "sample points: NULL pointer");
+  hipLaunchKernelGGL(k_sample_fwd, dim3(blocks_of(M, MRR_BLOCK)), dim3(MRR_BLOCK), 0, (hipStream_t)stream, verts, V,
+                     faces, F, face_idx, uv, M, points);
+  return launch_error("k_sample_fwd");
+}
+
+size_t mr_sample_points_backward_workspace(int64_t V) {
+  if (!mesh_sizes_ok(V, 0, 0)) return 0;
+  return carve_fix(nullptr, 3 * V).bytes;
+}
+
+int32_t mr_sample_points_backward(int64_t V, const int32_t* faces, int64_t F, const int32_t* face_idx, const float* uv,
+                                  int64_t M, const float* grad_points, float* grad_verts, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  if (!mesh_sizes_ok(V, F, M)) return mr_set_error_(MR_EINVAL, "sample points: V, F or the sample count out of range");
+  if (V == 0) return MR_OK;
+  if (!grad_verts || !ws || (M > 0 && (!face_idx || !uv || !grad_points)) || (F > 0 && !faces))
+    return mr_set_error_(MR_EINVAL, "sample points backward: NULL pointer");
+  const FixWS w = carve_fix(ws, 3 * V);
+  if (ws_bytes < w.bytes) return mr_set_error_(MR_EWORKSPACE, "sample points backward workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(ws, 0, w.bytes, st) != hipSuccess) return launch_error("sample points backward: memset");
+  if (M > 0 && F > 0) {
+    hipLaunchKernelGGL(k_sample_scatter, dim3(blocks_of(M, MRR_BLOCK)), dim3(MRR_BLOCK), 0, st, V, faces, F, face_idx,
+                       uv, M, grad_points, w.fix, w.rem);
+    if (int rc = launch_error("k_sample_scatter")) return rc;
+  }
+  hipLaunchKernelGGL(k_fix_to_float, dim3(blocks_of(3 * V, MRR_BLOCK)), dim3(MRR_BLOCK), 0, st, w.fix, w.rem, 3 * V,
+                     grad_verts);
+  return launch_error("k_fix_to_float");
+}
+
+int32_t mr_face_areas(const float* verts, int64_t V, const int32_t* faces, int64_t F, float* areas, void* stream) {
+  if (!mesh_sizes_ok(V, F, 0)) return mr_set_error_(MR_EINVAL, "face areas: V or F out of range");
+  if (F == 0) return MR_OK;
+  if (!verts || !faces || !areas) return mr_set_error_(MR_EINVAL, "face areas: NULL pointer");
+  hipLaunchKernelGGL(k_face_areas, dim3(blocks_of(F, MRR_BLOCK)), dim3(MRR_BLOCK), 0, (hipStream_t)stream, verts, V,
+                     faces, F, areas);
+  return launch_error("k_face_areas");
+}
+
+}  // extern "C"

@@ -224,6 +224,153 @@ class MeshShapePriors(torch.autograd.Function):
         return gv.to(dtype), None, None, None
 
 
+# --------------------------------------------------------------------------- point clouds (csrc/mr_points.hip)
+def _cloud_args(x, y, x_lengths, y_lengths, norm):
+    """Contiguous float32 clouds and int64 lengths of a pair of (N,P,3) batches, with their sizes."""
+    if x.dim() != 3 or y.dim() != 3:
+        raise ValueError("point clouds must be (N, P, D) tensors")
+    if x.shape[2] != 3 or y.shape[2] != 3:
+        raise NotImplementedError("point clouds: only D = 3 is built")
+    if x.shape[0] != y.shape[0]:
+        raise ValueError("y does not have the correct shape.")
+    if norm not in (1, 2):
+        raise ValueError("Support for 1 or 2 norm.")
+    N, P1, P2 = x.shape[0], x.shape[1], y.shape[1]
+    if N < 1 or P1 < 1 or P2 < 1:
+        raise ValueError("point clouds: N, P1 and P2 must be >= 1")
+    ls = []
+    for l in (x_lengths, y_lengths):
+        if l is not None:
+            if tuple(l.shape) != (N,):
+                raise ValueError("lengths must be of shape (N,)")
+            l = l.detach().to(torch.int64).contiguous()
+        ls.append(l)
+    _require_cuda(x, y, x_lengths, y_lengths)
+    return x.detach().float().contiguous(), y.detach().float().contiguous(), ls[0], ls[1], N, P1, P2
+
+
+def nearest_points(x, y, x_lengths=None, y_lengths=None, norm=2):
+    """(dist_x, idx_x, dist_y, idx_y): for every point of x (N,P1,3) the distance to and the index of its nearest
+    point of y (N,P2,3) (float32 / int32 (N,P1)), and the reverse ((N,P2)). norm 2: squared L2, norm 1: L1, in
+    float32 with a fixed operation order; equal distances take the lowest index. Entries past a length, or of a
+    cloud whose counterpart has length 0, are 0 / -1. No autograd; one memset and two launches (mr_nearest_points)."""
+    xf, yf, xl, yl, N, P1, P2 = _cloud_args(x, y, x_lengths, y_lengths, norm)
+    L = _lib.load()
+    dev = xf.device
+    dx, ix = torch.empty((N, P1), device=dev), torch.empty((N, P1), dtype=torch.int32, device=dev)
+    dy, iy = torch.empty((N, P2), device=dev), torch.empty((N, P2), dtype=torch.int32, device=dev)
+    wsb = _ws_size(L.mr_nearest_points_workspace, N, P1, P2)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    check(L.mr_nearest_points(ptr(xf), ptr(yf), N, P1, P2, ptr(xl), ptr(yl), int(norm), ptr(dx), ptr(ix), ptr(dy),
+                              ptr(iy), ptr(ws), wsb, _lib.stream_handle(dev)))
+    return dx, ix, dy, iy
+
+
+class ChamferDistance(torch.autograd.Function):
+    """The chamfer loss of x (N,P1,3) and y (N,P2,3) with the MR_CHAMFER_* ``flags`` reductions: one memset and
+    three launches forward (nearest neighbours of both directions, per-point reduce, final; mr_chamfer_forward), one
+    memset and two launches backward (fixed-point scatter, gradients; mr_chamfer_backward). Returns a 0-dim tensor,
+    or (N,) without a batch-reduction flag. Differentiable w.r.t. x and y (``weights`` is a constant)."""
+
+    @staticmethod
+    def forward(ctx, x, y, x_lengths, y_lengths, weights, flags, norm):
+        xf, yf, xl, yl, N, P1, P2 = _cloud_args(x, y, x_lengths, y_lengths, norm)
+        _require_cuda(weights)
+        L = _lib.load()
+        dev = xf.device
+        w = None if weights is None else weights.detach().float().contiguous()
+        want = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        single = bool(flags & _lib.MR_CHAMFER_SINGLE)
+        per_cloud = not (flags & (_lib.MR_CHAMFER_BATCH_MEAN | _lib.MR_CHAMFER_BATCH_SUM))
+        out = torch.empty(N if per_cloud else 1, device=dev)
+        ix = torch.empty((N, P1), dtype=torch.int32, device=dev) if want else None
+        iy = torch.empty((N, P2), dtype=torch.int32, device=dev) if want and not single else None
+        coef = torch.empty((2, N), device=dev) if want else None
+        wsb = _ws_size(L.mr_chamfer_workspace, N, P1, P2)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        check(L.mr_chamfer_forward(ptr(xf), ptr(yf), N, P1, P2, ptr(xl), ptr(yl), ptr(w), int(norm), int(flags),
+                                   ptr(ix), ptr(iy), ptr(coef), ptr(out), ptr(ws), wsb, _lib.stream_handle(dev)))
+        ctx.set_materialize_grads(False)
+        if want:
+            ctx.save_for_backward(xf, yf, ix, iy, coef)
+            ctx.args = (int(flags), int(norm), x.dtype, y.dtype)
+        return out if per_cloud else out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return (None,) * 7
+        xf, yf, ix, iy, coef = ctx.saved_tensors
+        flags, norm, xdt, ydt = ctx.args
+        g = g.detach().float().contiguous()
+        _require_cuda(g)
+        L = _lib.load()
+        N, P1, P2 = xf.shape[0], xf.shape[1], yf.shape[1]
+        gx, gy = torch.empty_like(xf), torch.empty_like(yf)
+        wsb = _ws_size(L.mr_chamfer_backward_workspace, N, P1, P2)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=xf.device)
+        check(L.mr_chamfer_backward(ptr(xf), ptr(yf), N, P1, P2, norm, flags, ptr(ix), ptr(iy), ptr(coef), ptr(g),
+                                    ptr(gx), ptr(gy), ptr(ws), wsb, _lib.stream_handle(xf.device)))
+        return gx.to(xdt), gy.to(ydt), None, None, None, None, None
+
+
+def _mesh_args(verts, faces):
+    _require_cuda(verts, faces)
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("verts must be (V, 3) and faces (F, 3)")
+    return verts.detach().float().contiguous(), faces.detach().to(torch.int32).contiguous()
+
+
+def face_areas(verts, faces):
+    """(F,) float32 areas 0.5 |(b - a) x (c - a)| of the packed faces (F,3) over verts (V,3); one launch, no
+    autograd (mr_face_areas)."""
+    v, f = _mesh_args(verts, faces)
+    areas = torch.empty(f.shape[0], device=v.device)
+    check(_lib.load().mr_face_areas(ptr(v), v.shape[0], ptr(f), f.shape[0], ptr(areas), _lib.stream_handle(v.device)))
+    return areas
+
+
+class SamplePoints(torch.autograd.Function):
+    """Points (N,S,3) on the packed faces (F,3) of verts (V,3): face ``face_idx`` (N,S) (negative: a row of zeros)
+    at the barycentric coordinates of ``uv`` (2,N,S) in [0,1) (upstream's _rand_barycentric_coords). One launch
+    forward (mr_sample_points_forward); the backward sums into the vertices with fixed-point integer atomics
+    (mr_sample_points_backward: a memset and two launches, bitwise reproducible). Differentiable w.r.t. verts."""
+
+    @staticmethod
+    def forward(ctx, verts, faces, face_idx, uv):
+        v, f = _mesh_args(verts, faces)
+        _require_cuda(face_idx, uv)
+        if face_idx.dim() != 2 or tuple(uv.shape) != (2,) + tuple(face_idx.shape):
+            raise ValueError("face_idx must be (N, S) and uv (2, N, S)")
+        fi = face_idx.detach().to(torch.int32).contiguous()
+        uvf = uv.detach().float().contiguous()
+        M = fi.numel()
+        pts = torch.empty(tuple(fi.shape) + (3,), device=v.device)
+        check(_lib.load().mr_sample_points_forward(ptr(v), v.shape[0], ptr(f), f.shape[0], ptr(fi), ptr(uvf), M,
+                                                   ptr(pts), _lib.stream_handle(v.device)))
+        ctx.set_materialize_grads(False)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(f, fi, uvf)
+            ctx.args = (v.shape[0], verts.dtype)
+        return pts
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None
+        f, fi, uvf = ctx.saved_tensors
+        V, dtype = ctx.args
+        g = g.detach().float().contiguous()
+        _require_cuda(g)
+        L = _lib.load()
+        gv = torch.empty((V, 3), device=g.device)
+        wsb = _ws_size(L.mr_sample_points_backward_workspace, V)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=g.device)
+        check(L.mr_sample_points_backward(V, ptr(f), f.shape[0], ptr(fi), ptr(uvf), fi.numel(), ptr(g), ptr(gv),
+                                          ptr(ws), wsb, _lib.stream_handle(g.device)))
+        return gv.to(dtype), None, None, None
+
+
 def raster_settings_struct(H, W, K=1, blur=0.0, persp=True, clip=False, cull=False, max_faces_per_bin=None,
                            z_clip=None):
     """mr_raster_settings_t; z_clip = z_clip_value of the near-plane clip (None: no clipping)."""

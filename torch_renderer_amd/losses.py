@@ -1,4 +1,9 @@
-"""Fused losses: the pose optimiser's loss and the mesh shape priors of the deformation loops.
+"""Fused losses: the pose optimiser's loss, the mesh shape priors of the deformation loops and the chamfer distance.
+
+Chamfer distance (``pytorch3d.loss.chamfer_distance`` as the geometry-fitting loops call it on sampled points,
+mesh_deformer.py:299-352, deform_mesh_from_pcd.py:160-212, and on whole clouds, chamfer_loss_evaluation.py:126):
+``chamfer_distance`` is one autograd node over a tiled nearest-neighbour kernel that keeps the targets in LDS and
+never writes the (N, P1, P2) distance matrix (kernels.ChamferDistance, csrc/mr_points.hip). Deterministic.
 
 Mesh shape priors (``pytorch3d.loss.mesh_edge_loss`` / ``mesh_laplacian_smoothing`` / ``mesh_normal_consistency``,
 called together by update_mesh_shape_prior_losses at deform_mesh_with_color.py:248-256 and mesh_deformer.py:
@@ -32,7 +37,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .kernels import MeshShapePriors, _require_cuda, mesh_prior_topology
+from .kernels import ChamferDistance, MeshShapePriors, _require_cuda, mesh_prior_topology
 
 
 def _rgba_base(t: torch.Tensor, channels):
@@ -114,3 +119,47 @@ def mesh_normal_consistency(meshes):
     """pytorch3d.loss.mesh_normal_consistency: per mesh the mean over the pairs of faces sharing an edge of
     1 - cos(angle between their normals), averaged over the meshes (0 for a mesh without such pairs)."""
     return _mesh_priors(meshes, 0.0, _lib.MR_PRIOR_NORMAL)[2]
+
+
+def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_normals=None, weights=None,
+                     batch_reduction="mean", point_reduction="mean", norm: int = 2, single_directional: bool = False):
+    """pytorch3d.loss.chamfer_distance for (N,P,3) tensors: per cloud the sum (``point_reduction="sum"``) or the mean
+    over max(length, 1) points (``"mean"``) of every point's distance to its nearest point of the other cloud
+    (squared L2 for ``norm=2``, L1 for ``norm=1``), x -> y plus y -> x (x -> y alone with ``single_directional``),
+    times ``weights`` (N,); then summed over the batch (``batch_reduction="sum"``), divided by sum(weights) or N
+    (``"mean"``), or left as (N,) (``None``). Returns ``(loss, None)``: normals are not built. Differentiable
+    w.r.t. x and y (``weights`` is a constant); given lengths are checked on the host, otherwise nothing
+    synchronises."""
+    if x_normals is not None or y_normals is not None:
+        raise NotImplementedError("chamfer_distance: normals are not built")
+    if point_reduction is None:
+        raise NotImplementedError("chamfer_distance: point_reduction=None is not built")
+    if batch_reduction is not None and batch_reduction not in ("mean", "sum"):
+        raise ValueError('batch_reduction must be one of ["mean", "sum"] or None')
+    if point_reduction not in ("mean", "sum"):
+        raise ValueError('point_reduction must be one of ["mean", "sum"] or None')
+    if norm not in (1, 2):
+        raise ValueError("Support for 1 or 2 norm.")
+    if not torch.is_tensor(x) or not torch.is_tensor(y):
+        raise NotImplementedError("chamfer_distance: only (N, P, 3) tensors are built (no Pointclouds)")
+    if x.dim() != 3 or y.dim() != 3:
+        raise ValueError("Expected points to be of shape (N, P, D)")
+    if x.shape[2] != 3 or y.shape[2] != 3:
+        raise NotImplementedError("chamfer_distance: only D = 3 is built")
+    N = x.shape[0]
+    if y.shape[0] != N:
+        raise ValueError("y does not have the correct shape.")
+    if weights is not None and tuple(weights.shape) != (N,):
+        raise ValueError("weights must be of shape (N,).")
+    for name, l, P in (("x_lengths", x_lengths, x.shape[1]), ("y_lengths", y_lengths, y.shape[1])):
+        if l is None:
+            continue
+        if tuple(l.shape) != (N,):
+            raise ValueError(f"{name} must be of shape (N,).")
+        if N and (int(l.min()) < 0 or int(l.max()) > P):  # reads the lengths on the host
+            raise ValueError(f"{name}: a length is outside [0, {P}]")
+    _require_cuda(x, y, x_lengths, y_lengths, weights)
+    flags = (_lib.MR_CHAMFER_POINT_MEAN if point_reduction == "mean" else 0) | \
+        {None: 0, "mean": _lib.MR_CHAMFER_BATCH_MEAN, "sum": _lib.MR_CHAMFER_BATCH_SUM}[batch_reduction] | \
+        (_lib.MR_CHAMFER_SINGLE if single_directional else 0)
+    return ChamferDistance.apply(x, y, x_lengths, y_lengths, weights, flags, norm), None
