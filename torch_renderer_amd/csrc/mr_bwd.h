@@ -922,7 +922,5 @@ static int launch_bwd_fused(const RenderBwdParams& P, int64_t NT, hipStream_t st
   if (!grid) grid = resident_grid(k_bwd_fused<ACC, CLIP, GEO, SPEC>, 256, GEO ? 4 : ACC == 27 ? 2 : 3);
   const int gr = grid * MR_BWD_GRID_MUL;
   const int c = (int)(NT / 4 + 1 < gr ? NT / 4 + 1 : gr);
-  MR_TIMED(KID_BWD_FUSED, st, (k_bwd_fused<ACC, CLIP, GEO, SPEC><<<(c + 7) / 8 * 8, 256, 0, st>>>(P)));
-  MR_CHECK_LAUNCH("k_bwd_fused");
-  return MR_OK;
+  return launch(KID_BWD_FUSED, "k_bwd_fused", k_bwd_fused<ACC, CLIP, GEO, SPEC>, (c + 7) / 8 * 8, 256, 0, st, P);
 }

@@ -45,6 +45,27 @@ MR_DEV float fpow(float a, float b) { return a > 0.0f ? __builtin_amdgcn_exp2f(b
 #define MR_FIX_MAX 16777216.0f  // 2^24
 MR_DEV long long fix_of(float x) { return __float2ll_rn(x * 4294967296.0f); }
 MR_DEV float fix_to_f(unsigned long long v) { return (float)((double)(long long)v * (1.0 / 4294967296.0)); }
+// A scatter's rows (the point-cloud and sampling backwards): adds v to fixed-point word i, or to the float
+// remainder when |v| >= MR_FIX_MAX (non-finite addends too); the total of component i afterwards.
+MR_DEV void fix_add(unsigned long long* __restrict__ fix, float* __restrict__ rem, int64_t i, float v) {
+  if (v == 0.0f) return;
+  if (fabsf(v) < MR_FIX_MAX) atomicAdd(&fix[i], (unsigned long long)fix_of(v));
+  else atomicAdd(&rem[i], v);
+}
+MR_DEV float fix_read(const unsigned long long* __restrict__ fix, const float* __restrict__ rem, int64_t i) {
+  return fix_to_f(fix[i]) + rem[i];
+}
+
+// Sum of a double over a 256-thread workgroup in a fixed tree (xor butterflies inside each wave, then the four
+// waves in order); sm: 4 doubles of LDS.
+MR_DEV double block_sum(double v, double* sm) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const double t = ((sm[0] + sm[1]) + sm[2]) + sm[3];
+  __syncthreads();
+  return t;
+}
 // Columns of a face's gradient-total row: ACC = 18 holds the three corners' position then normal columns
 // (3 c + k, 9 + 3 c + k); ACC = 27 (vertex colours) keeps each corner's position and colour columns adjacent
 // (6 c + k, 6 c + 3 + k; normals 18 + 3 c + k), so that a vertex gathers one 48-B piece of each incident face's

@@ -498,55 +498,48 @@ __global__ void __launch_bounds__(1024) k_slot_order(const int* __restrict__ ctr
 }
 
 template <int KP, bool SIL = false>
-static void launch_raster_kr(const FwdParams& P, int64_t slots_cap, hipStream_t st) {
-  if (slots_cap >= (1ll << 31)) return;
-  MR_TIMED(KID_RASTER_K, st, (k_raster_kp<KP, SIL><<<(unsigned)slots_cap, 64, 0, st>>>(P)));  // one wave per tile
+static int launch_raster_kr(const FwdParams& P, int64_t slots_cap, hipStream_t st) {
+  if (slots_cap >= (1ll << 31)) return MR_OK;
+  return launch(KID_RASTER_K, SIL ? "k_raster_kp (silhouette)" : "k_raster_kr", k_raster_kp<KP, SIL>, (unsigned)slots_cap,
+                64, 0, st, P);  // one wave per tile
 }
-// The fused soft silhouette's raster (K <= 64, register lists).
+// One instantiation per K range (register lists, K <= 64).
+template <bool SIL>
+static int launch_raster_kr_for(const FwdParams& P, int64_t sc, hipStream_t st) {
+  const int K = P.K;
+  if (K <= 4) return launch_raster_kr<4, SIL>(P, sc, st);
+  if (K <= 8) return launch_raster_kr<8, SIL>(P, sc, st);
+  if (K <= 16) return launch_raster_kr<16, SIL>(P, sc, st);
+  if (K <= 32) return launch_raster_kr<32, SIL>(P, sc, st);
+  if (K <= 50) return launch_raster_kr<50, SIL>(P, sc, st);
+  return launch_raster_kr<64, SIL>(P, sc, st);
+}
 // The heaviest tile lists first: one wave per tile and more tiles than wave slots, so the waves that start
 // last set the kernel's tail; started first, the long lists overlap the many short ones (LPT order).
-static void slot_order(FwdParams& P, hipStream_t st) {
-  if (!MR_KP_ORDER || !P.sorder_ws) return;
-  k_slot_order<<<1, 1024, 0, st>>>(P.ctr, P.stile, P.cnt, P.sorder_ws);
+static int slot_order(FwdParams& P, hipStream_t st) {
+  if (!MR_KP_ORDER || !P.sorder_ws) return MR_OK;
   P.sorder = P.sorder_ws;
+  return launch(KID_NONE, "k_slot_order", k_slot_order, 1, 1024, 0, st, P.ctr, P.stile, P.cnt, P.sorder_ws);
 }
-static void launch_raster_sil(FwdParams P, const BinGeom& g, int64_t N, hipStream_t st) {
-  slot_order(P, st);
-  const int K = P.K;
-  const int64_t sc = N * (int64_t)g.T;
-  if (K <= 4) launch_raster_kr<4, true>(P, sc, st);
-  else if (K <= 8) launch_raster_kr<8, true>(P, sc, st);
-  else if (K <= 16) launch_raster_kr<16, true>(P, sc, st);
-  else if (K <= 32) launch_raster_kr<32, true>(P, sc, st);
-  else if (K <= 50) launch_raster_kr<50, true>(P, sc, st);
-  else launch_raster_kr<64, true>(P, sc, st);
+// The fused soft silhouette's raster (K <= 64, register lists).
+static int launch_raster_sil(FwdParams P, const BinGeom& g, int64_t N, hipStream_t st) {
+  if (int rc = slot_order(P, st)) return rc;
+  return launch_raster_kr_for<true>(P, N * (int64_t)g.T, st);
 }
-
 
 static int launch_raster_k(FwdParams P, const BinGeom& g, int64_t N, hipStream_t st) {
   static int fgrid = 0;
   if (!fgrid) fgrid = resident_grid(k_fill<0, 3>, 256, 8);
-  MR_TIMED(KID_FILL_FRAG, st, (k_fill<0, 3><<<fgrid, 256, 0, st>>>(P)));
-  MR_CHECK_LAUNCH("k_fill");
+  if (int rc = launch(KID_FILL_FRAG, "k_fill", k_fill<0, 3>, fgrid, 256, 0, st, P)) return rc;
   const int K = P.K;
   if (K <= 64) {  // keys in registers (k_raster_kr)
-    slot_order(P, st);
-    const int64_t sc = N * (int64_t)g.T;
-    if (K <= 4) launch_raster_kr<4>(P, sc, st);
-    else if (K <= 8) launch_raster_kr<8>(P, sc, st);
-    else if (K <= 16) launch_raster_kr<16>(P, sc, st);
-    else if (K <= 32) launch_raster_kr<32>(P, sc, st);
-    else if (K <= 50) launch_raster_kr<50>(P, sc, st);
-    else launch_raster_kr<64>(P, sc, st);
-    MR_CHECK_LAUNCH("k_raster_kr");
-    return MR_OK;
+    if (int rc = slot_order(P, st)) return rc;
+    return launch_raster_kr_for<false>(P, N * (int64_t)g.T, st);
   }
   const size_t wb = (size_t)K * 64 * 8 + 64 * sizeof(FaceRec) + 64 * sizeof(int);
   const int wpg = wb * 4 <= 65536 ? 4 : wb * 2 <= 65536 ? 2 : 1;
   const int64_t slots_cap = N * (int64_t)g.T;
   const int64_t want = (slots_cap + wpg - 1) / wpg;
   const int grid = (int)(want < 8192 ? want : 8192);
-  MR_TIMED(KID_RASTER_K, st, (k_raster_k<<<grid, 64 * wpg, wb * wpg, st>>>(P)));
-  MR_CHECK_LAUNCH("k_raster_k");
-  return MR_OK;
+  return launch(KID_RASTER_K, "k_raster_k", k_raster_k, grid, 64 * wpg, wb * wpg, st, P);
 }

@@ -23,12 +23,10 @@
 //   k_sample_fwd / k_sample_scatter / k_fix_to_float, k_face_areas: see the entry points below.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/mi355r.h"
 #include "mr_common.h"
-
-extern "C" int mr_set_error_(int code, const char* msg);  // mr_raster.hip: the library's thread-local error text
+#include "mr_host.h"
 
 #define MRN_BLOCK 128                  // threads of a k_nn workgroup (two waves)
 #define MRN_Q 4                        // queries per thread
@@ -51,8 +49,6 @@ struct NNGeom {
   int64_t groups[2];   // workgroups of direction d per cloud
 };
 
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
 bool sizes_ok(int64_t N, int64_t P1, int64_t P2) {
   // per-cloud indices are int32; the grid's y dimension is the batch
   return N >= 1 && P1 >= 1 && P2 >= 1 && N <= 65535 && P1 < 0x7fffffffll && P2 < 0x7fffffffll &&
@@ -66,7 +62,7 @@ NNGeom nn_geom(int64_t N, int64_t P1, int64_t P2) {
   g.P[1] = P2;
   for (int d = 0; d < 2; ++d) {
     const int64_t Pq = g.P[d], Pt = g.P[1 - d];
-    const int64_t qtiles = (Pq + MRN_QT - 1) / MRN_QT;
+    const int64_t qtiles = ceil_div(Pq, MRN_QT);
     int64_t want = MRN_WANT_GROUPS / (N * qtiles);
     if (want < 1) want = 1;
     int64_t c = ((Pt + want - 1) / want + 63) / 64 * 64;
@@ -87,19 +83,13 @@ struct PointsWS {
 };
 PointsWS carve_points(void* base, int64_t N, int64_t P1, int64_t P2) {
   PointsWS w;
-  char* b = (char*)base;
-  size_t off = 0;
-  w.key[0] = (u64*)(b + off);
-  off += sizeof(u64) * (size_t)(N * P1);
-  w.key[1] = (u64*)(b + off);
-  off += sizeof(u64) * (size_t)(N * P2);
-  w.key_bytes = off;
-  off = align256(off);
-  const int64_t pm = P1 > P2 ? P1 : P2;
-  w.nblk = (pm + MRR_TILE - 1) / MRR_TILE;
-  w.part = (double*)(b + off);
-  off = align256(off + sizeof(double) * 2 * (size_t)(N * w.nblk));
-  w.bytes = off;
+  Carver c(base);
+  w.key[0] = c.take_packed<u64>((size_t)(N * P1));  // the two key arrays back to back: one memset
+  w.key[1] = c.take<u64>((size_t)(N * P2));
+  w.key_bytes = sizeof(u64) * (size_t)(N * (P1 + P2));
+  w.nblk = ceil_div(P1 > P2 ? P1 : P2, MRR_TILE);
+  w.part = c.take<double>(2 * (size_t)(N * w.nblk));
+  w.bytes = c.off;
   return w;
 }
 
@@ -111,9 +101,10 @@ struct FixWS {
 };
 FixWS carve_fix(void* base, int64_t n) {
   FixWS w;
-  w.fix = (u64*)base;
-  w.rem = (float*)((char*)base + sizeof(u64) * (size_t)n);
-  w.bytes = align256((sizeof(u64) + sizeof(float)) * (size_t)n);
+  Carver c(base);
+  w.fix = c.take_packed<u64>((size_t)n);  // words and remainders back to back: one memset
+  w.rem = c.take<float>((size_t)n);
+  w.bytes = c.off;
   return w;
 }
 
@@ -181,16 +172,6 @@ __global__ void __launch_bounds__(MRN_BLOCK) k_nn(const float* __restrict__ x, c
     const int64_t i = q0 + k * MRN_BLOCK + threadIdx.x;
     if (i < lq) atomicMin(&key[i], ((u64)__float_as_uint(best[k]) << 32) | (u64)(uint32_t)(t0 + bi[k]));
   }
-}
-
-// Sum over the workgroup in a fixed tree (xor butterflies inside each wave, then the four waves in order).
-__device__ __forceinline__ double block_sum(double v, double* sm) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double t = ((sm[0] + sm[1]) + sm[2]) + sm[3];
-  __syncthreads();
-  return t;
 }
 
 // grid (nblk, N, directions). dist / idx / part may each be NULL.
@@ -266,13 +247,6 @@ __global__ void __launch_bounds__(MRR_BLOCK) k_cham_final(const double* __restri
   if (!per_cloud && threadIdx.x == 0) out[0] = (float)(total * scale);
 }
 
-// Adds v to fixed-point word i (or to the float remainder when |v| >= MR_FIX_MAX; non-finite addends too).
-__device__ __forceinline__ void fix_add(u64* __restrict__ fix, float* __restrict__ rem, int64_t i, float v) {
-  if (v == 0.0f) return;
-  if (fabsf(v) < MR_FIX_MAX) atomicAdd(&fix[i], (u64)fix_of(v));
-  else atomicAdd(&rem[i], v);
-}
-
 __device__ __forceinline__ float sgn(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }
 
 // grid (blocks over max(P1, P2), N, directions): point i of direction d's queries adds its difference to its
@@ -331,7 +305,7 @@ __global__ void __launch_bounds__(MRR_BLOCK) k_cham_grad(const float* __restrict
       const float df = q[c] - t[c];
       own = NORM == 2 ? df : sgn(df);
     }
-    const float other = fix_to_f(fix[row + c]) + rem[row + c];
+    const float other = fix_read(fix, rem, row + c);
     out[c] = c_own * own - c_other * other;
   }
 }
@@ -396,7 +370,7 @@ __global__ void __launch_bounds__(MRR_BLOCK) k_sample_scatter(int64_t V, const i
 __global__ void __launch_bounds__(MRR_BLOCK) k_fix_to_float(const u64* __restrict__ fix, const float* __restrict__ rem,
                                                             int64_t n, float* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * MRR_BLOCK + threadIdx.x;
-  if (i < n) out[i] = fix_to_f(fix[i]) + rem[i];
+  if (i < n) out[i] = fix_read(fix, rem, i);
 }
 
 __global__ void __launch_bounds__(MRR_BLOCK) k_face_areas(const float* __restrict__ verts, int64_t V,
@@ -418,34 +392,12 @@ __global__ void __launch_bounds__(MRR_BLOCK) k_face_areas(const float* __restric
   areas[f] = area;
 }
 
-int launch_error(const char* name) {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return MR_OK;
-  char msg[256];
-  snprintf(msg, sizeof(msg), "%s: %s", name, hipGetErrorString(e));
-  return mr_set_error_(MR_ELAUNCH, msg);
-}
-
-inline unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
 int check_clouds(const char* who, const float* x, const float* y, int64_t N, int64_t P1, int64_t P2, int32_t norm) {
-  char msg[160];
-  if (N < 1 || P1 < 1 || P2 < 1) {
-    snprintf(msg, sizeof(msg), "%s: N, P1 and P2 must be >= 1", who);
-    return mr_set_error_(MR_EINVAL, msg);
-  }
-  if (!sizes_ok(N, P1, P2)) {
-    snprintf(msg, sizeof(msg), "%s: more than 65535 clouds or clouds too large for 32-bit point ids", who);
-    return mr_set_error_(MR_EUNSUPPORTED, msg);
-  }
-  if (norm != 1 && norm != 2) {
-    snprintf(msg, sizeof(msg), "%s: norm must be 1 or 2", who);
-    return mr_set_error_(MR_EINVAL, msg);
-  }
-  if (!x || !y) {
-    snprintf(msg, sizeof(msg), "%s: x / y is NULL", who);
-    return mr_set_error_(MR_EINVAL, msg);
-  }
+  if (N < 1 || P1 < 1 || P2 < 1) return set_err(MR_EINVAL, "%s: N, P1 and P2 must be >= 1", who);
+  if (!sizes_ok(N, P1, P2))
+    return set_err(MR_EUNSUPPORTED, "%s: more than 65535 clouds or clouds too large for 32-bit point ids", who);
+  if (norm != 1 && norm != 2) return set_err(MR_EINVAL, "%s: norm must be 1 or 2", who);
+  if (!x || !y) return set_err(MR_EINVAL, "%s: x / y is NULL", who);
   return MR_OK;
 }
 
@@ -453,13 +405,11 @@ int check_clouds(const char* who, const float* x, const float* y, int64_t N, int
 int run_nn(const float* x, const float* y, const NNGeom& g, const int64_t* xl, const int64_t* yl, int32_t norm, int dirs,
            const PointsWS& w, hipStream_t st) {
   if (g.groups[0] > 0x7fffffffll || g.groups[1] > 0x7fffffffll)
-    return mr_set_error_(MR_EUNSUPPORTED, "nearest points: P1 * P2 is too large for one launch");
-  if (hipMemsetAsync(w.key[0], 0xff, w.key_bytes, st) != hipSuccess) return launch_error("nearest points: memset");
+    return set_err(MR_EUNSUPPORTED, "nearest points: P1 * P2 is too large for one launch");
+  if (int rc = memset_async(w.key[0], 0xff, w.key_bytes, st)) return rc;
   const int64_t gx = (dirs == 2 && g.groups[1] > g.groups[0]) ? g.groups[1] : g.groups[0];
   const dim3 grid((unsigned)gx, (unsigned)g.N, (unsigned)dirs);
-  if (norm == 2) hipLaunchKernelGGL(k_nn<2>, grid, dim3(MRN_BLOCK), 0, st, x, y, g, xl, yl, w.key[0], w.key[1]);
-  else hipLaunchKernelGGL(k_nn<1>, grid, dim3(MRN_BLOCK), 0, st, x, y, g, xl, yl, w.key[0], w.key[1]);
-  return launch_error("k_nn");
+  return launch(KID_NONE, "k_nn", norm == 2 ? k_nn<2> : k_nn<1>, grid, MRN_BLOCK, 0, st, x, y, g, xl, yl, w.key[0], w.key[1]);
 }
 
 bool mesh_sizes_ok(int64_t V, int64_t F, int64_t M) {
@@ -480,15 +430,14 @@ int32_t mr_nearest_points(const float* x, const float* y, int64_t N, int64_t P1,
                           int32_t* idx_y, void* ws, size_t ws_bytes, void* stream) {
   if (int rc = check_clouds("nearest points", x, y, N, P1, P2, norm)) return rc;
   if (!dist_x || !idx_x || !dist_y || !idx_y || !ws)
-    return mr_set_error_(MR_EINVAL, "nearest points: an output or the workspace is NULL");
+    return set_err(MR_EINVAL, "nearest points: an output or the workspace is NULL");
   const PointsWS w = carve_points(ws, N, P1, P2);
-  if (ws_bytes < w.bytes) return mr_set_error_(MR_EWORKSPACE, "nearest points workspace too small");
+  if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "nearest points workspace too small");
   const hipStream_t st = (hipStream_t)stream;
   const NNGeom g = nn_geom(N, P1, P2);
   if (int rc = run_nn(x, y, g, x_lengths, y_lengths, norm, 2, w, st)) return rc;
-  hipLaunchKernelGGL(k_nn_reduce, dim3((unsigned)w.nblk, (unsigned)N, 2), dim3(MRR_BLOCK), 0, st, g, x_lengths,
-                     y_lengths, w.key[0], w.key[1], dist_x, idx_x, dist_y, idx_y, (double*)nullptr, w.nblk);
-  return launch_error("k_nn_reduce");
+  return launch(KID_NONE, "k_nn_reduce", k_nn_reduce, dim3((unsigned)w.nblk, (unsigned)N, 2), MRR_BLOCK, 0, st, g, x_lengths,
+                y_lengths, w.key[0], w.key[1], dist_x, idx_x, dist_y, idx_y, nullptr, w.nblk);
 }
 
 size_t mr_chamfer_workspace(int64_t N, int64_t P1, int64_t P2) { return mr_nearest_points_workspace(N, P1, P2); }
@@ -498,21 +447,19 @@ int32_t mr_chamfer_forward(const float* x, const float* y, int64_t N, int64_t P1
                            int32_t* idx_y, float* coef, float* out, void* ws, size_t ws_bytes, void* stream) {
   if (int rc = check_clouds("chamfer", x, y, N, P1, P2, norm)) return rc;
   if ((flags & ~MR_CHAMFER_ALL) || ((flags & MR_CHAMFER_BATCH_MEAN) && (flags & MR_CHAMFER_BATCH_SUM)))
-    return mr_set_error_(MR_EINVAL, "chamfer: unknown or contradictory bits in flags");
-  if (!out || !ws) return mr_set_error_(MR_EINVAL, "chamfer: out / workspace is NULL");
+    return set_err(MR_EINVAL, "chamfer: unknown or contradictory bits in flags");
+  if (!out || !ws) return set_err(MR_EINVAL, "chamfer: out / workspace is NULL");
   const PointsWS w = carve_points(ws, N, P1, P2);
-  if (ws_bytes < w.bytes) return mr_set_error_(MR_EWORKSPACE, "chamfer workspace too small");
+  if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "chamfer workspace too small");
   const hipStream_t st = (hipStream_t)stream;
   const int dirs = (flags & MR_CHAMFER_SINGLE) ? 1 : 2;
   const NNGeom g = nn_geom(N, P1, P2);
   if (int rc = run_nn(x, y, g, x_lengths, y_lengths, norm, dirs, w, st)) return rc;
-  hipLaunchKernelGGL(k_nn_reduce, dim3((unsigned)w.nblk, (unsigned)N, (unsigned)dirs), dim3(MRR_BLOCK), 0, st, g,
-                     x_lengths, y_lengths, w.key[0], w.key[1], (float*)nullptr, idx_x, (float*)nullptr, idx_y, w.part,
-                     w.nblk);
-  if (int rc = launch_error("k_nn_reduce")) return rc;
-  hipLaunchKernelGGL(k_cham_final, dim3(1), dim3(MRR_BLOCK), 0, st, w.part, w.nblk, N, P1, P2, x_lengths, y_lengths,
-                     weights, flags, out, coef);
-  return launch_error("k_cham_final");
+  if (int rc = launch(KID_NONE, "k_nn_reduce", k_nn_reduce, dim3((unsigned)w.nblk, (unsigned)N, (unsigned)dirs), MRR_BLOCK, 0,
+                      st, g, x_lengths, y_lengths, w.key[0], w.key[1], nullptr, idx_x, nullptr, idx_y, w.part, w.nblk))
+    return rc;
+  return launch(KID_NONE, "k_cham_final", k_cham_final, 1, MRR_BLOCK, 0, st, w.part, w.nblk, N, P1, P2, x_lengths, y_lengths,
+                weights, flags, out, coef);
 }
 
 size_t mr_chamfer_backward_workspace(int64_t N, int64_t P1, int64_t P2) {
@@ -525,41 +472,33 @@ int32_t mr_chamfer_backward(const float* x, const float* y, int64_t N, int64_t P
                             const float* grad_out, float* grad_x, float* grad_y, void* ws, size_t ws_bytes,
                             void* stream) {
   if (int rc = check_clouds("chamfer backward", x, y, N, P1, P2, norm)) return rc;
-  if (flags & ~MR_CHAMFER_ALL) return mr_set_error_(MR_EINVAL, "chamfer backward: unknown bits in flags");
+  if (flags & ~MR_CHAMFER_ALL) return set_err(MR_EINVAL, "chamfer backward: unknown bits in flags");
   const bool single = flags & MR_CHAMFER_SINGLE;
   if (!idx_x || (!single && !idx_y) || !coef || !grad_out || !grad_x || !grad_y || !ws)
-    return mr_set_error_(MR_EINVAL, "chamfer backward: NULL pointer");
+    return set_err(MR_EINVAL, "chamfer backward: NULL pointer");
   const FixWS w = carve_fix(ws, 3 * N * (P1 + P2));
-  if (ws_bytes < w.bytes) return mr_set_error_(MR_EWORKSPACE, "chamfer backward workspace too small");
+  if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "chamfer backward workspace too small");
   const hipStream_t st = (hipStream_t)stream;
   if (single) idx_y = nullptr;
-  if (hipMemsetAsync(ws, 0, w.bytes, st) != hipSuccess) return launch_error("chamfer backward: memset");
+  if (int rc = memset_async(ws, 0, w.bytes, st)) return rc;
   const int per_cloud = !(flags & (MR_CHAMFER_BATCH_MEAN | MR_CHAMFER_BATCH_SUM));
-  const unsigned nb = blocks_of(P1 > P2 ? P1 : P2, MRR_BLOCK);
-  const dim3 gs(nb, (unsigned)N, single ? 1u : 2u), gg(nb, (unsigned)N, 2u), blk(MRR_BLOCK);
-  if (norm == 2) {
-    hipLaunchKernelGGL(k_cham_scatter<2>, gs, blk, 0, st, x, y, N, P1, P2, idx_x, idx_y, w.fix, w.rem);
-    if (int rc = launch_error("k_cham_scatter")) return rc;
-    hipLaunchKernelGGL(k_cham_grad<2>, gg, blk, 0, st, x, y, N, P1, P2, idx_x, idx_y, coef, grad_out, per_cloud,
-                       w.fix, w.rem, grad_x, grad_y);
-  } else {
-    hipLaunchKernelGGL(k_cham_scatter<1>, gs, blk, 0, st, x, y, N, P1, P2, idx_x, idx_y, w.fix, w.rem);
-    if (int rc = launch_error("k_cham_scatter")) return rc;
-    hipLaunchKernelGGL(k_cham_grad<1>, gg, blk, 0, st, x, y, N, P1, P2, idx_x, idx_y, coef, grad_out, per_cloud,
-                       w.fix, w.rem, grad_x, grad_y);
-  }
-  return launch_error("k_cham_grad");
+  const unsigned nb = ceil_div(P1 > P2 ? P1 : P2, MRR_BLOCK);
+  const dim3 gs(nb, (unsigned)N, single ? 1u : 2u), gg(nb, (unsigned)N, 2u);
+  if (int rc = launch(KID_NONE, "k_cham_scatter", norm == 2 ? k_cham_scatter<2> : k_cham_scatter<1>, gs, MRR_BLOCK, 0, st, x, y,
+                      N, P1, P2, idx_x, idx_y, w.fix, w.rem))
+    return rc;
+  return launch(KID_NONE, "k_cham_grad", norm == 2 ? k_cham_grad<2> : k_cham_grad<1>, gg, MRR_BLOCK, 0, st, x, y, N, P1, P2,
+                idx_x, idx_y, coef, grad_out, per_cloud, w.fix, w.rem, grad_x, grad_y);
 }
 
 int32_t mr_sample_points_forward(const float* verts, int64_t V, const int32_t* faces, int64_t F,
                                  const int32_t* face_idx, const float* uv, int64_t M, float* points, void* stream) {
-  if (!mesh_sizes_ok(V, F, M)) return mr_set_error_(MR_EINVAL, "sample points: V, F or the sample count out of range");
+  if (!mesh_sizes_ok(V, F, M)) return set_err(MR_EINVAL, "sample points: V, F or the sample count out of range");
   if (M == 0) return MR_OK;
   if (!face_idx || !uv || !points || (F > 0 && (!faces || !verts)))
-    return mr_set_error_(MR_EINVAL, "sample points: NULL pointer");
-  hipLaunchKernelGGL(k_sample_fwd, dim3(blocks_of(M, MRR_BLOCK)), dim3(MRR_BLOCK), 0, (hipStream_t)stream, verts, V,
-                     faces, F, face_idx, uv, M, points);
-  return launch_error("k_sample_fwd");
+    return set_err(MR_EINVAL, "sample points: NULL pointer");
+  return launch(KID_NONE, "k_sample_fwd", k_sample_fwd, ceil_div(M, MRR_BLOCK), MRR_BLOCK, 0, (hipStream_t)stream, verts, V,
+                faces, F, face_idx, uv, M, points);
 }
 
 size_t mr_sample_points_backward_workspace(int64_t V) {
@@ -570,31 +509,28 @@ size_t mr_sample_points_backward_workspace(int64_t V) {
 int32_t mr_sample_points_backward(int64_t V, const int32_t* faces, int64_t F, const int32_t* face_idx, const float* uv,
                                   int64_t M, const float* grad_points, float* grad_verts, void* ws, size_t ws_bytes,
                                   void* stream) {
-  if (!mesh_sizes_ok(V, F, M)) return mr_set_error_(MR_EINVAL, "sample points: V, F or the sample count out of range");
+  if (!mesh_sizes_ok(V, F, M)) return set_err(MR_EINVAL, "sample points: V, F or the sample count out of range");
   if (V == 0) return MR_OK;
   if (!grad_verts || !ws || (M > 0 && (!face_idx || !uv || !grad_points)) || (F > 0 && !faces))
-    return mr_set_error_(MR_EINVAL, "sample points backward: NULL pointer");
+    return set_err(MR_EINVAL, "sample points backward: NULL pointer");
   const FixWS w = carve_fix(ws, 3 * V);
-  if (ws_bytes < w.bytes) return mr_set_error_(MR_EWORKSPACE, "sample points backward workspace too small");
+  if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "sample points backward workspace too small");
   const hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(ws, 0, w.bytes, st) != hipSuccess) return launch_error("sample points backward: memset");
-  if (M > 0 && F > 0) {
-    hipLaunchKernelGGL(k_sample_scatter, dim3(blocks_of(M, MRR_BLOCK)), dim3(MRR_BLOCK), 0, st, V, faces, F, face_idx,
-                       uv, M, grad_points, w.fix, w.rem);
-    if (int rc = launch_error("k_sample_scatter")) return rc;
-  }
-  hipLaunchKernelGGL(k_fix_to_float, dim3(blocks_of(3 * V, MRR_BLOCK)), dim3(MRR_BLOCK), 0, st, w.fix, w.rem, 3 * V,
-                     grad_verts);
-  return launch_error("k_fix_to_float");
+  if (int rc = memset_async(ws, 0, w.bytes, st)) return rc;
+  if (M > 0 && F > 0)
+    if (int rc = launch(KID_NONE, "k_sample_scatter", k_sample_scatter, ceil_div(M, MRR_BLOCK), MRR_BLOCK, 0, st, V, faces, F,
+                        face_idx, uv, M, grad_points, w.fix, w.rem))
+      return rc;
+  return launch(KID_NONE, "k_fix_to_float", k_fix_to_float, ceil_div(3 * V, MRR_BLOCK), MRR_BLOCK, 0, st, w.fix, w.rem, 3 * V,
+                grad_verts);
 }
 
 int32_t mr_face_areas(const float* verts, int64_t V, const int32_t* faces, int64_t F, float* areas, void* stream) {
-  if (!mesh_sizes_ok(V, F, 0)) return mr_set_error_(MR_EINVAL, "face areas: V or F out of range");
+  if (!mesh_sizes_ok(V, F, 0)) return set_err(MR_EINVAL, "face areas: V or F out of range");
   if (F == 0) return MR_OK;
-  if (!verts || !faces || !areas) return mr_set_error_(MR_EINVAL, "face areas: NULL pointer");
-  hipLaunchKernelGGL(k_face_areas, dim3(blocks_of(F, MRR_BLOCK)), dim3(MRR_BLOCK), 0, (hipStream_t)stream, verts, V,
-                     faces, F, areas);
-  return launch_error("k_face_areas");
+  if (!verts || !faces || !areas) return set_err(MR_EINVAL, "face areas: NULL pointer");
+  return launch(KID_NONE, "k_face_areas", k_face_areas, ceil_div(F, MRR_BLOCK), MRR_BLOCK, 0, (hipStream_t)stream, verts, V,
+                faces, F, areas);
 }
 
 }  // extern "C"

@@ -21,11 +21,12 @@
 // vectors on a flat one; a few thousand elements' worth of double arithmetic costs less than a launch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
+
+#include <algorithm>
 
 #include "../../include/mi355r.h"
-
-extern "C" int mr_set_error_(int code, const char* msg);  // mr_raster.hip: the library's thread-local error text
+#include "mr_common.h"
+#include "mr_host.h"
 
 #define MRP_BLOCK 256
 
@@ -54,34 +55,18 @@ struct PriorsWS {
   float4* prow;  // (4 P) weighted gradient of pair p's term w.r.t. its vertex of role r (e0, e1, a, b) at 4 p + r
   size_t bytes;
 };
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-inline int64_t max3(int64_t a, int64_t b, int64_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
 inline int64_t fwd_blocks(int64_t V, int64_t E, int64_t P) {
-  const int64_t n = max3(V, E, P);
-  return n > 0 ? (n + MRP_BLOCK - 1) / MRP_BLOCK : 1;
+  const int64_t n = std::max({V, E, P});
+  return n > 0 ? ceil_div(n, MRP_BLOCK) : 1;
 }
 PriorsWS carve_priors(void* base, int64_t V, int64_t E, int64_t P) {
   PriorsWS w;
-  char* b = (char*)base;
-  size_t off = 0;
-  w.part = (double*)(b + off);
-  off = align256(off + sizeof(double) * 3 * (size_t)fwd_blocks(V, E, P));
-  w.lapu = (float4*)(b + off);
-  off = align256(off + sizeof(float4) * (size_t)V);
-  w.prow = (float4*)(b + off);
-  off = align256(off + sizeof(float4) * 4 * (size_t)P);
-  w.bytes = off;
+  Carver c(base);
+  w.part = c.take<double>(3 * (size_t)fwd_blocks(V, E, P));
+  w.lapu = c.take<float4>((size_t)V);
+  w.prow = c.take<float4>(4 * (size_t)P);
+  w.bytes = c.off;
   return w;
-}
-
-// Sum over the workgroup in a fixed tree (xor butterflies inside each wave, then the four waves in order).
-__device__ __forceinline__ double block_sum(double v, double* sm) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double t = ((sm[0] + sm[1]) + sm[2]) + sm[3];
-  __syncthreads();
-  return t;
 }
 
 __global__ void __launch_bounds__(MRP_BLOCK) k_priors_fwd(
@@ -214,14 +199,6 @@ __global__ void __launch_bounds__(MRP_BLOCK) k_priors_bwd(
   grad[3 * i + 2] = (float)g.z;
 }
 
-int launch_error(const char* name) {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return MR_OK;
-  char msg[256];
-  snprintf(msg, sizeof(msg), "%s: %s", name, hipGetErrorString(e));
-  return mr_set_error_(MR_ELAUNCH, msg);
-}
-
 bool sizes_ok(int64_t V, int64_t E, int64_t P) {
   // element ids and CSR offsets are int32 (4 P pair rows, 2 E neighbour entries)
   return V >= 0 && E >= 0 && P >= 0 && V < 0x7fffffffll / 3 && E < 0x3fffffffll && P < 0x1fffffffll;
@@ -240,42 +217,40 @@ int32_t mr_mesh_priors_forward(const float* verts, int64_t V, const int32_t* edg
                                const int32_t* nbr_ptr, const int32_t* nbr, const float* vert_w, const int32_t* pairs,
                                const float* pair_w, int64_t P, float target_length, int32_t terms, int32_t want_grad,
                                float* out, void* ws, size_t ws_bytes, void* stream) {
-  if (!sizes_ok(V, E, P)) return mr_set_error_(MR_EINVAL, "mesh priors: V, E or P out of range");
-  if (terms & ~MR_PRIOR_ALL) return mr_set_error_(MR_EINVAL, "mesh priors: unknown bits in terms");
-  if (!out || !ws) return mr_set_error_(MR_EINVAL, "mesh priors: out / workspace is NULL");
+  if (!sizes_ok(V, E, P)) return set_err(MR_EINVAL, "mesh priors: V, E or P out of range");
+  if (terms & ~MR_PRIOR_ALL) return set_err(MR_EINVAL, "mesh priors: unknown bits in terms");
+  if (!out || !ws) return set_err(MR_EINVAL, "mesh priors: out / workspace is NULL");
   if ((V > 0 && (!verts || !nbr_ptr || !vert_w)) || (E > 0 && (!edges || !edge_w || !nbr)) ||
       (P > 0 && (!pairs || !pair_w)))
-    return mr_set_error_(MR_EINVAL, "mesh priors: NULL topology or vertex pointer");
+    return set_err(MR_EINVAL, "mesh priors: NULL topology or vertex pointer");
   const PriorsWS w = carve_priors(ws, V, E, P);
-  if (ws_bytes < w.bytes) return mr_set_error_(MR_EWORKSPACE, "mesh priors workspace too small");
+  if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "mesh priors workspace too small");
   const hipStream_t st = (hipStream_t)stream;
   const int64_t nb = fwd_blocks(V, E, P);
-  hipLaunchKernelGGL(k_priors_fwd, dim3((unsigned)nb), dim3(MRP_BLOCK), 0, st, verts, V, (const int2*)edges, edge_w, E,
-                     nbr_ptr, nbr, (const float2*)vert_w, (const int4*)pairs, pair_w, P, target_length, terms, w.part,
-                     want_grad ? w.lapu : nullptr, want_grad ? w.prow : nullptr);
-  if (int rc = launch_error("k_priors_fwd")) return rc;
-  hipLaunchKernelGGL(k_priors_final, dim3(1), dim3(MRP_BLOCK), 0, st, w.part, nb, out);
-  return launch_error("k_priors_final");
+  if (int rc = launch(KID_NONE, "k_priors_fwd", k_priors_fwd, (unsigned)nb, MRP_BLOCK, 0, st, verts, V, (const int2*)edges,
+                      edge_w, E, nbr_ptr, nbr, (const float2*)vert_w, (const int4*)pairs, pair_w, P, target_length, terms,
+                      w.part, want_grad ? w.lapu : nullptr, want_grad ? w.prow : nullptr))
+    return rc;
+  return launch(KID_NONE, "k_priors_final", k_priors_final, 1, MRP_BLOCK, 0, st, w.part, nb, out);
 }
 
 int32_t mr_mesh_priors_backward(const float* verts, int64_t V, const int32_t* nbr_ptr, const int32_t* nbr,
                                 const float* vert_w, const int32_t* pair_ptr, const int32_t* pair_idx, int64_t E,
                                 int64_t P, float target_length, int32_t terms, const float* g_edge, const float* g_lap,
                                 const float* g_norm, const void* fwd_ws, float* grad_verts, void* stream) {
-  if (!sizes_ok(V, E, P)) return mr_set_error_(MR_EINVAL, "mesh priors: V, E or P out of range");
-  if (terms & ~MR_PRIOR_ALL) return mr_set_error_(MR_EINVAL, "mesh priors: unknown bits in terms");
+  if (!sizes_ok(V, E, P)) return set_err(MR_EINVAL, "mesh priors: V, E or P out of range");
+  if (terms & ~MR_PRIOR_ALL) return set_err(MR_EINVAL, "mesh priors: unknown bits in terms");
   if (V == 0) return MR_OK;
   if (!verts || !nbr_ptr || !vert_w || !pair_ptr || !fwd_ws || !grad_verts || (E > 0 && !nbr) || (P > 0 && !pair_idx))
-    return mr_set_error_(MR_EINVAL, "mesh priors backward: NULL pointer");
+    return set_err(MR_EINVAL, "mesh priors backward: NULL pointer");
   // a term the forward did not compute left no rows in the workspace: its upstream gradient is ignored
   if (!(terms & MR_PRIOR_EDGE)) g_edge = nullptr;
   if (!(terms & MR_PRIOR_LAPLACIAN)) g_lap = nullptr;
   if (!(terms & MR_PRIOR_NORMAL)) g_norm = nullptr;
   const PriorsWS w = carve_priors((void*)fwd_ws, V, E, P);
-  hipLaunchKernelGGL(k_priors_bwd, dim3((unsigned)((V + MRP_BLOCK - 1) / MRP_BLOCK)), dim3(MRP_BLOCK), 0,
-                     (hipStream_t)stream, verts, V, nbr_ptr, nbr, (const float2*)vert_w, pair_ptr, pair_idx,
-                     target_length, g_edge, g_lap, g_norm, w.lapu, w.prow, grad_verts);
-  return launch_error("k_priors_bwd");
+  return launch(KID_NONE, "k_priors_bwd", k_priors_bwd, ceil_div(V, MRP_BLOCK), MRP_BLOCK, 0, (hipStream_t)stream, verts, V,
+                nbr_ptr, nbr, (const float2*)vert_w, pair_ptr, pair_idx, target_length, g_edge, g_lap, g_norm, w.lapu, w.prow,
+                grad_verts);
 }
 
 }  // extern "C"

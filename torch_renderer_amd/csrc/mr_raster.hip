@@ -1,5 +1,6 @@
-// mi355r — MI355X (gfx950, CDNA4) rasterizer kernels + C ABI (one translation unit: the stage headers
-// below are included in order; this file holds the extern "C" entry points of include/mi355r.h).
+// mi355r — MI355X (gfx950, CDNA4) rasterizer kernels + C ABI (the render's translation unit: the stage headers
+// below are included in order; this file holds the render's extern "C" entry points of include/mi355r.h, and
+// the library's error text and timing pool, which mr_host.h declares for mr_priors.hip and mr_points.hip too).
 //
 // Pipeline for a batch of N views (all launches async on one stream, no host sync):
 //   1. binning (mr_bin.h): k_bin_rect_world projects every (view, face) — pose conversion (cv_view_elem,
@@ -26,19 +27,20 @@
 // Host side: an entry point checks its arguments, fills the kernels' parameter structs (make_setup, make_fwd,
 // make_shade, make_raster_bwd; cv_poses for pose arrays; render_call for what the fused forward and its reshade
 // share) and calls one launcher per kernel family, which owns that family's template ladder, grid and timing
-// id: launch_bin_rect_world, launch_bin_view, launch_scan and launch_views_from_cv here,
+// id; every launch goes through mr_host.h's launch(), every workspace layout through its Carver:
+// launch_bin_rect_world, launch_bin_view, launch_scan and launch_views_from_cv here,
 // launch_raster_and_shade / launch_fill_and_shade (mr_tile_raster.h), launch_raster_k (mr_kdeep.h),
 // launch_bwd_fused (mr_bwd.h) and launch_vertex_grads (mr_vertex.h) beside their kernels.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
-#include <stdarg.h>
 #include <stdlib.h>
 
 #include "../../include/mi355r.h"
 #include "mr_common.h"
 #include "mr_shade.h"
 
+#include "mr_host.h"
 #include "mr_runtime.h"
 #include "mr_bin.h"
 #include "mr_tile_raster.h"
@@ -48,90 +50,13 @@
 #include "mr_frag_shade.h"
 #include "mr_loss.h"
 
-// ---------------------------------------------------------------------------
-// C ABI
-// ---------------------------------------------------------------------------
-extern "C" {
+// The library's one error text and one timing pool (declared in mr_host.h for every translation unit).
+__thread char g_err[512];
+TimingPool g_t;
+#define MR_KID_NAME(id, name) name,
+static const char* const kKernelNames[KID_COUNT] = {MR_KERNEL_IDS(MR_KID_NAME)};
+#undef MR_KID_NAME
 
-const char* mr_last_error(void) { return g_err; }
-// for the library's other translation units (mr_priors.hip): set this thread's error text, return `code`
-int mr_set_error_(int code, const char* msg) { return set_err(code, "%s", msg); }
-
-
-int32_t mr_version(void) { return 5; }
-
-int32_t mr_struct_size(int32_t which) {
-  switch (which) {
-    case 0: return (int32_t)sizeof(mr_view_t);
-    case 1: return (int32_t)sizeof(mr_raster_settings_t);
-    case 2: return (int32_t)sizeof(mr_shade_params_t);
-    case 3: return (int32_t)sizeof(mr_mesh_t);
-    default: return -1;
-  }
-}
-
-static int check_settings(const mr_raster_settings_t* s) {
-  if (!s) return set_err(MR_EINVAL, "settings is NULL");
-  if (s->H <= 0 || s->W <= 0) return set_err(MR_EINVAL, "image size must be positive (got %d x %d)", s->H, s->W);
-  if (s->H > 8192 || s->W > 8192) return set_err(MR_EUNSUPPORTED, "image size above 8192");
-  if (s->faces_per_pixel < 1 || s->faces_per_pixel > MR_KMAX)
-    return set_err(MR_EUNSUPPORTED, "faces_per_pixel=%d: supported range is [1, %d]", s->faces_per_pixel, MR_KMAX);
-  if (!(s->blur_radius >= 0.0f) || !__builtin_isfinite(s->blur_radius))
-    return set_err(MR_EINVAL, "blur_radius must be finite and >= 0");
-  return MR_OK;
-}
-
-size_t mr_rasterize_meshes_workspace(int64_t num_meshes, int64_t total_faces, int32_t H, int32_t W,
-                                     int32_t max_faces_per_bin) {
-  const int64_t Ftot = total_faces > 0 ? total_faces : 1;
-  BinGeom g = bin_geom(H, W, num_meshes, Ftot, max_faces_per_bin);
-  return carve_raster_ws(nullptr, num_meshes, Ftot, g).bytes;
-}
-
-static SetupParams make_setup(const mr_raster_settings_t* s, const BinGeom& g, const RasterWS& w) {
-  SetupParams P;
-  memset(&P, 0, sizeof(P));
-  P.H = s->H; P.W = s->W; P.TX = g.TX; P.TY = g.TY; P.T = g.T;
-  P.bbox_pad = sqrtf(s->blur_radius);
-  P.persp = s->perspective_correct;
-  P.cull = s->cull_backfaces;
-  P.clipz = s->clip_z != 0;
-  P.zc = s->z_clip_value;
-  P.NF = 0;  // set by the caller
-  P.crec = w.crec;
-  P.list_cap = g.list_cap;
-  P.recs = w.recs;
-  P.cnt = w.cnt;
-  P.cur = w.cur;
-  P.list = w.list;
-  P.vtot = w.vtot;
-  P.vbase = w.vbase;
-  P.rects = w.rects;
-  P.fv_out = nullptr;
-  P.vff = nullptr;
-  P.bcnt = w.bcnt;
-  P.nbcnt = w.nbcnt;
-  return P;
-}
-
-static int launch_scan(const RasterWS& w, int64_t N, const BinGeom& g, const int64_t* view_count, int64_t F,
-                       hipStream_t st) {
-  ScanParams P;
-  P.T = g.T; P.mfpb = g.mfpb; P.list_cap = g.list_cap;
-  P.cnt = w.cnt; P.vtot = w.vtot; P.start = w.start; P.cur = w.cur; P.vbase = w.vbase;
-  P.tdone = w.tdone; P.vslot = w.vslot; P.stile = w.stile; P.units = w.units; P.ctr = w.ctr; P.tkey = w.tkey;
-  P.view_count = view_count; P.F = F;
-  MR_TIMED(KID_BIN_SCAN, st, (k_bin_scan<<<(unsigned)N, 1024, 0, st>>>(P)));
-  MR_CHECK_LAUNCH("k_bin_scan");
-  return MR_OK;
-}
-
-// The per-view binning applies to tile grids of <= MR_VIEW_TMAX tiles (<= 256 a side) and
-// meshes of <= MR_VIEW_FMAX faces per view on average; else count -> scan -> fill.
-static bool view_binning(const BinGeom& g, int64_t N, int64_t Ftot) {
-  return g.T <= MR_VIEW_TMAX && g.TX <= 256 && g.TY <= 256 && Ftot <= (int64_t)MR_VIEW_FMAX * N;
-}
-extern "C++" {
 // Background chunks per wave of k_bin_view's background workgroups (measured on the bench
 // workloads, profiles/r2e_bg_ab.txt): beyond these the stores slow the view workgroups' binning
 // more than they shorten the raster.
@@ -222,9 +147,9 @@ static int launch_bin_view(const SetupParams& SP, const RasterWS& w, const BinGe
   V.units = w.units; V.ctr = w.ctr; V.tkey = w.tkey; V.list = w.list;
   if (B > 1 && !first && !view_count && w.nbcnt == N * B && F > 0) {
     // one shared mesh: each band's records listed first (the record launch cleared the counts)
-    MR_TIMED(KID_BAND_BUCKET, st, (k_band_bucket<<<dim3((unsigned)ceil_div(F, 1024), (unsigned)N), 1024, 0, st>>>(
-                                       w.rects, F, SP.NF, SP.clipz ? 2 : 1, g.TY, B, w.bcnt, w.blist, w.bcap)));
-    MR_CHECK_LAUNCH("k_band_bucket");
+    if (int rc = launch(KID_BAND_BUCKET, "k_band_bucket", k_band_bucket, dim3((unsigned)ceil_div(F, 1024), (unsigned)N),
+                        1024, 0, st, w.rects, F, SP.NF, SP.clipz ? 2 : 1, g.TY, B, w.bcnt, w.blist, w.bcap))
+      return rc;
     V.blist = w.blist;
     V.bcnt = w.bcnt;
     V.bcap = w.bcap;
@@ -237,27 +162,98 @@ static int launch_bin_view(const SetupParams& SP, const RasterWS& w, const BinGe
     const int64_t nbg = bin_bg_wgs(nbin, sb, B > 1);
     if (Pf && nbg > 0 && (MODE != 0 || Pf->K == 1)) {
       Pf->fill_first = (int)bg_chunks(N, nbin, sb, Pf->H, Pf->W, MODE);
-      MR_TIMED(KID_BIN_VIEW, st, (k_bin_view<MODE, CH><<<(unsigned)(nbin + sb + nbg), 1024, shm, st>>>(V, *Pf)));
-      MR_CHECK_LAUNCH("k_bin_view");
-      return MR_OK;
+      return launch(KID_BIN_VIEW, "k_bin_view", k_bin_view<MODE, CH>, (unsigned)(nbin + sb + nbg), 1024, shm, st, V, *Pf);
     }
   }
-  MR_TIMED(KID_BIN_VIEW, st, (k_bin_view<<<(unsigned)(nbin + sb), 1024, shm, st>>>(V)));
-  MR_CHECK_LAUNCH("k_bin_view");
+  return launch<ViewBinParams>(KID_BIN_VIEW, "k_bin_view", k_bin_view, (unsigned)(nbin + sb), 1024, shm, st, V);
+}
+
+// ---------------------------------------------------------------------------
+// C ABI
+// ---------------------------------------------------------------------------
+extern "C" {
+
+const char* mr_last_error(void) { return g_err; }
+
+int32_t mr_version(void) { return 5; }
+
+int32_t mr_struct_size(int32_t which) {
+  switch (which) {
+    case 0: return (int32_t)sizeof(mr_view_t);
+    case 1: return (int32_t)sizeof(mr_raster_settings_t);
+    case 2: return (int32_t)sizeof(mr_shade_params_t);
+    case 3: return (int32_t)sizeof(mr_mesh_t);
+    default: return -1;
+  }
+}
+
+static int check_settings(const mr_raster_settings_t* s) {
+  if (!s) return set_err(MR_EINVAL, "settings is NULL");
+  if (s->H <= 0 || s->W <= 0) return set_err(MR_EINVAL, "image size must be positive (got %d x %d)", s->H, s->W);
+  if (s->H > 8192 || s->W > 8192) return set_err(MR_EUNSUPPORTED, "image size above 8192");
+  if (s->faces_per_pixel < 1 || s->faces_per_pixel > MR_KMAX)
+    return set_err(MR_EUNSUPPORTED, "faces_per_pixel=%d: supported range is [1, %d]", s->faces_per_pixel, MR_KMAX);
+  if (!(s->blur_radius >= 0.0f) || !__builtin_isfinite(s->blur_radius))
+    return set_err(MR_EINVAL, "blur_radius must be finite and >= 0");
   return MR_OK;
 }
-}  // extern "C++"
 
+size_t mr_rasterize_meshes_workspace(int64_t num_meshes, int64_t total_faces, int32_t H, int32_t W,
+                                     int32_t max_faces_per_bin) {
+  const int64_t Ftot = total_faces > 0 ? total_faces : 1;
+  BinGeom g = bin_geom(H, W, num_meshes, Ftot, max_faces_per_bin);
+  return carve_raster_ws(nullptr, num_meshes, Ftot, g).bytes;
+}
+
+static SetupParams make_setup(const mr_raster_settings_t* s, const BinGeom& g, const RasterWS& w) {
+  SetupParams P;
+  memset(&P, 0, sizeof(P));
+  P.H = s->H; P.W = s->W; P.TX = g.TX; P.TY = g.TY; P.T = g.T;
+  P.bbox_pad = sqrtf(s->blur_radius);
+  P.persp = s->perspective_correct;
+  P.cull = s->cull_backfaces;
+  P.clipz = s->clip_z != 0;
+  P.zc = s->z_clip_value;
+  P.NF = 0;  // set by the caller
+  P.crec = w.crec;
+  P.list_cap = g.list_cap;
+  P.recs = w.recs;
+  P.cnt = w.cnt;
+  P.cur = w.cur;
+  P.list = w.list;
+  P.vtot = w.vtot;
+  P.vbase = w.vbase;
+  P.rects = w.rects;
+  P.fv_out = nullptr;
+  P.vff = nullptr;
+  P.bcnt = w.bcnt;
+  P.nbcnt = w.nbcnt;
+  return P;
+}
+
+static int launch_scan(const RasterWS& w, int64_t N, const BinGeom& g, const int64_t* view_count, int64_t F,
+                       hipStream_t st) {
+  ScanParams P;
+  P.T = g.T; P.mfpb = g.mfpb; P.list_cap = g.list_cap;
+  P.cnt = w.cnt; P.vtot = w.vtot; P.start = w.start; P.cur = w.cur; P.vbase = w.vbase;
+  P.tdone = w.tdone; P.vslot = w.vslot; P.stile = w.stile; P.units = w.units; P.ctr = w.ctr; P.tkey = w.tkey;
+  P.view_count = view_count; P.F = F;
+  return launch(KID_BIN_SCAN, "k_bin_scan", k_bin_scan, (unsigned)N, 1024, 0, st, P);
+}
+
+// The per-view binning applies to tile grids of <= MR_VIEW_TMAX tiles (<= 256 a side) and
+// meshes of <= MR_VIEW_FMAX faces per view on average; else count -> scan -> fill.
+static bool view_binning(const BinGeom& g, int64_t N, int64_t Ftot) {
+  return g.T <= MR_VIEW_TMAX && g.TX <= 256 && g.TY <= 256 && Ftot <= (int64_t)MR_VIEW_FMAX * N;
+}
 // k_bin_rect_world<clip_z> over `grid`: row 0 the clears (and NA's normals), rows 1 .. N the views' records,
 // rows past them B's background chunks.
 static int launch_bin_rect_world(const SetupParams& SP, dim3 grid, const float* verts, const int32_t* faces, int64_t F,
                                  const mr_view_t* views, const NormalsArgs& NA, int* ctr, const CvPoses& C,
                                  const FragBg& B, hipStream_t st) {
   const ViewRec* vr = (const ViewRec*)views;
-  if (SP.clipz) MR_TIMED(KID_BIN_RECT, st, (k_bin_rect_world<true><<<grid, 256, 0, st>>>(SP, verts, faces, F, vr, NA, ctr, C, B)));
-  else MR_TIMED(KID_BIN_RECT, st, (k_bin_rect_world<false><<<grid, 256, 0, st>>>(SP, verts, faces, F, vr, NA, ctr, C, B)));
-  MR_CHECK_LAUNCH("k_bin_rect_world");
-  return MR_OK;
+  return launch(KID_BIN_RECT, "k_bin_rect_world", SP.clipz ? k_bin_rect_world<true> : k_bin_rect_world<false>, grid, 256, 0,
+                st, SP, verts, faces, F, vr, NA, ctr, C, B);
 }
 
 // The pose arrays of mr_poses_t / mr_opencv_poses_t (one layout, two conventions) as the kernels' CvPoses,
@@ -284,9 +280,8 @@ __global__ void __launch_bounds__(256) k_views_from_cv(CvPoses C, int64_t N, int
   }
 }
 static int launch_views_from_cv(const CvPoses& C, int64_t N, hipStream_t st, int64_t F = 0, int64_t* first = nullptr) {
-  k_views_from_cv<<<ceil_div(N * 16, 256), 256, 0, st>>>(C, N, F, first, first ? first + N : nullptr);
-  MR_CHECK_LAUNCH("k_views_from_cv");
-  return MR_OK;
+  return launch(KID_NONE, "k_views_from_cv", k_views_from_cv, ceil_div(N * 16, 256), 256, 0, st, C, N, F, first,
+                first ? first + N : nullptr);
 }
 
 int32_t mr_per_view_binning(int64_t N, int64_t total_faces, int32_t H, int32_t W) {
@@ -322,8 +317,7 @@ int32_t mr_rasterize_meshes(const float* face_verts, const int64_t* first, const
   if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "workspace too small: %zu < %zu", ws_bytes, w.bytes);
   const bool vpath = view_binning(g, N, Fb);
   // per-view path: k_bin_rect_fv clears the counters
-  if ((!vpath || Ftot == 0) && hipMemsetAsync(w.ctr, 0, zero_bytes(N, g, vpath), st) != hipSuccess)
-    return set_err(MR_ELAUNCH, "memset failed");
+  if ((!vpath || Ftot == 0) && (rc = memset_async(w.ctr, 0, zero_bytes(N, g, vpath), st))) return rc;
   SetupParams SP = make_setup(s, g, w);
   FwdParams P = make_fwd(s, g, w, N, first, 0, Fb);
   P.p2f = p2f; P.zbuf = zbuf; P.bary = bary; P.dists = dists;
@@ -332,11 +326,9 @@ int32_t mr_rasterize_meshes(const float* face_verts, const int64_t* first, const
   const size_t shm = lds ? sizeof(int) * (size_t)g.T : 0;
   SP.NF = Fb;
   if (vpath) {
-    if (Ftot > 0) {
-      if (SP.clipz) MR_TIMED(KID_BIN_RECT, st, (k_bin_rect_fv<true><<<ceil_div(Ftot, 256), 256, 0, st>>>(SP, face_verts, Ftot, w.ctr)));
-      else MR_TIMED(KID_BIN_RECT, st, (k_bin_rect_fv<false><<<ceil_div(Ftot, 256), 256, 0, st>>>(SP, face_verts, Ftot, w.ctr)));
-      MR_CHECK_LAUNCH("k_bin_rect_fv");
-    }
+    if (Ftot > 0 && (rc = launch(KID_BIN_RECT, "k_bin_rect_fv", SP.clipz ? k_bin_rect_fv<true> : k_bin_rect_fv<false>,
+                                 ceil_div(Ftot, 256), 256, 0, st, SP, face_verts, Ftot, w.ctr)))
+      return rc;
     if (s->faces_per_pixel > 1) {
       if ((rc = launch_bin_view(SP, w, g, N, first, count, 0, true, st))) return rc;
       return launch_raster_k(P, g, N, st);
@@ -346,17 +338,13 @@ int32_t mr_rasterize_meshes(const float* face_verts, const int64_t* first, const
     return launch_raster_and_shade<0, 3>(P, g, N, st, s->clip_z != 0);
   }
   const int fvb = ceil_div(Ftot, 256 * MR_FV_FPT);
-  if (Ftot > 0) {
-    if (lds) MR_TIMED(KID_BIN_COUNT, st, (k_bin_count_fv<true><<<fvb, 256, shm, st>>>(SP, face_verts, Ftot, first, N)));
-    else MR_TIMED(KID_BIN_COUNT, st, (k_bin_count_fv<false><<<fvb, 256, 0, st>>>(SP, face_verts, Ftot, first, N)));
-    MR_CHECK_LAUNCH("k_bin_count_fv");
-  }
+  if (Ftot > 0 && (rc = launch(KID_BIN_COUNT, "k_bin_count_fv", lds ? k_bin_count_fv<true> : k_bin_count_fv<false>, fvb, 256,
+                               shm, st, SP, face_verts, Ftot, first, N)))
+    return rc;
   if ((rc = launch_scan(w, N, g, count, 0, st))) return rc;
-  if (Ftot > 0) {
-    if (lds) MR_TIMED(KID_BIN_FILL, st, (k_bin_fill_fv<true><<<fvb, 256, shm, st>>>(SP, Ftot, first, N)));
-    else MR_TIMED(KID_BIN_FILL, st, (k_bin_fill_fv<false><<<fvb, 256, 0, st>>>(SP, Ftot, first, N)));
-    MR_CHECK_LAUNCH("k_bin_fill_fv");
-  }
+  if (Ftot > 0 && (rc = launch(KID_BIN_FILL, "k_bin_fill_fv", lds ? k_bin_fill_fv<true> : k_bin_fill_fv<false>, fvb, 256, shm,
+                               st, SP, Ftot, first, N)))
+    return rc;
   if (s->faces_per_pixel > 1) return launch_raster_k(P, g, N, st);
   return launch_raster_and_shade<0, 3>(P, g, N, st, s->clip_z != 0);
 }
@@ -441,13 +429,10 @@ struct SilWS {
 };
 static SilWS carve_sil(void* base, size_t raster_bytes, int64_t NT, int K) {
   SilWS w;
-  char* b = (char*)base;
-  size_t off = align_up(raster_bytes, 256);
-  w.spix = (float4*)(b + off);
-  off = align_up(off + sizeof(float4) * 64 * (size_t)NT, 256);
-  w.sent = (int4*)(b + off);
-  off = align_up(off + sizeof(int4) * 64 * (size_t)K * (size_t)NT, 256);
-  w.bytes = off;
+  Carver c(base, align_up(raster_bytes, 256));
+  w.spix = c.take<float4>(64 * (size_t)NT);
+  w.sent = c.take<int4>(64 * (size_t)K * (size_t)NT);
+  w.bytes = c.off;
   return w;
 }
 size_t mr_soft_silhouette_workspace(int64_t N, int64_t F, int32_t H, int32_t W, int32_t K, int32_t max_faces_per_bin) {
@@ -495,9 +480,7 @@ int32_t mr_soft_silhouette_forward(const float* verts, int64_t V, const int32_t*
   dim3 rgrid((unsigned)ceil_div(F, 256), (unsigned)N + 1);  // row 0: counter clear
   if ((rc = launch_bin_rect_world(SP, rgrid, verts, faces, F, views_out, NA, w.ctr, C, FragBg{}, st))) return rc;
   if ((rc = launch_bin_view(SP, w, g, N, nullptr, nullptr, F, true, st))) return rc;
-  launch_raster_sil(P, g, N, st);
-  MR_CHECK_LAUNCH("k_raster_kp (silhouette)");
-  return MR_OK;
+  return launch_raster_sil(P, g, N, st);
 }
 
 // The modular backwards' parameters from the settings; the upstream gradient pointers are the caller's.
@@ -523,8 +506,7 @@ int32_t mr_soft_silhouette_backward(const float* face_verts, int64_t N, int64_t 
   if (K < 2 || K > 64 || !(sigma > 0.0f)) return set_err(MR_EINVAL, "bad faces_per_pixel / sigma");
   hipStream_t st = (hipStream_t)stream;
   const int64_t Fb = N * F;
-  if (hipMemsetAsync(grad_face_verts, 0, sizeof(float) * 9 * (size_t)Fb, st) != hipSuccess)
-    return set_err(MR_ELAUNCH, "memset failed");
+  if ((rc = memset_async(grad_face_verts, 0, sizeof(float) * 9 * (size_t)Fb, st))) return rc;
   BinGeom g = bin_geom(s->H, s->W, N, Fb, s->max_faces_per_bin);
   RasterWS w = carve_raster_ws((void*)ws, N, Fb, g);
   SilWS sw = carve_sil((void*)ws, w.bytes, N * (int64_t)g.T, K);
@@ -536,9 +518,7 @@ int32_t mr_soft_silhouette_backward(const float* face_verts, int64_t N, int64_t 
   P.grad_rgba = grad_rgba;
   static int grid = 0;
   if (!grid) grid = resident_grid(k_sil_bwd, 256, 8);
-  MR_TIMED(KID_RASTER_BWD, st, (k_sil_bwd<<<grid, 256, 0, st>>>(P)));
-  MR_CHECK_LAUNCH("k_sil_bwd");
-  return MR_OK;
+  return launch(KID_RASTER_BWD, "k_sil_bwd", k_sil_bwd, grid, 256, 0, st, P);
 }
 
 int32_t mr_rasterize_meshes_backward(const float* fv, const int64_t* p2f, const float* gz, const float* gb,
@@ -549,15 +529,12 @@ int32_t mr_rasterize_meshes_backward(const float* fv, const int64_t* p2f, const 
   if (N <= 0 || N > 65535) return set_err(MR_EINVAL, "num_meshes out of range");
   if (!p2f || !gfv) return set_err(MR_EINVAL, "NULL tensor argument");
   hipStream_t st = (hipStream_t)stream;
-  if (Ftot > 0 && hipMemsetAsync(gfv, 0, sizeof(float) * 9 * (size_t)Ftot, st) != hipSuccess)
-    return set_err(MR_ELAUNCH, "memset failed");
+  if (Ftot > 0 && (rc = memset_async(gfv, 0, sizeof(float) * 9 * (size_t)Ftot, st))) return rc;
   if (Ftot == 0 || (!gz && !gb && !gd)) return MR_OK;  // NULL gradients are zero
   RasterBwdParams P = make_raster_bwd(s, N, fv, gfv);
   P.p2f = p2f; P.gz = gz; P.gb = gb; P.gd = gd;
   const int64_t nslots = N * (int64_t)s->H * s->W * s->faces_per_pixel;
-  MR_TIMED(KID_RASTER_BWD, st, (k_raster_bwd_slots<<<(unsigned)((nslots + 255) / 256), 256, 0, st>>>(P, nslots)));
-  MR_CHECK_LAUNCH("k_raster_bwd");
-  return MR_OK;
+  return launch(KID_RASTER_BWD, "k_raster_bwd", k_raster_bwd_slots, (unsigned)((nslots + 255) / 256), 256, 0, st, P, nslots);
 }
 
 int32_t mr_project_faces(const float* verts, int64_t V, const int32_t* faces, int64_t F, const mr_view_t* views,
@@ -566,9 +543,8 @@ int32_t mr_project_faces(const float* verts, int64_t V, const int32_t* faces, in
   if (F == 0) return MR_OK;
   if (!verts || !faces || !views || !fv) return set_err(MR_EINVAL, "NULL argument");
   dim3 grid(ceil_div(F, 256), (unsigned)N);
-  MR_TIMED(KID_PROJECT, (hipStream_t)stream, (k_project_faces<<<grid, 256, 0, (hipStream_t)stream>>>(verts, faces, F, (const ViewRec*)views, fv, nullptr)));
-  MR_CHECK_LAUNCH("k_project_faces");
-  return MR_OK;
+  return launch(KID_PROJECT, "k_project_faces", k_project_faces, grid, 256, 0, (hipStream_t)stream, verts, faces, F,
+                (const ViewRec*)views, fv, nullptr);
 }
 
 int32_t mr_project_faces_meshes(const float* verts, int64_t V, const int32_t* faces, int64_t F,
@@ -578,9 +554,8 @@ int32_t mr_project_faces_meshes(const float* verts, int64_t V, const int32_t* fa
   if (F == 0 || max_view_faces == 0) return MR_OK;
   if (!verts || !faces || !views || !fv || !view_face_first) return set_err(MR_EINVAL, "NULL argument");
   dim3 grid(ceil_div(max_view_faces, 256), (unsigned)N);
-  MR_TIMED(KID_PROJECT, (hipStream_t)stream, (k_project_faces<<<grid, 256, 0, (hipStream_t)stream>>>(verts, faces, F, (const ViewRec*)views, fv, view_face_first)));
-  MR_CHECK_LAUNCH("k_project_faces");
-  return MR_OK;
+  return launch(KID_PROJECT, "k_project_faces", k_project_faces, grid, 256, 0, (hipStream_t)stream, verts, faces, F,
+                (const ViewRec*)views, fv, view_face_first);
 }
 
 int32_t mr_project_faces_backward(const float* verts, int64_t V, const int32_t* faces, int64_t F,
@@ -589,15 +564,13 @@ int32_t mr_project_faces_backward(const float* verts, int64_t V, const int32_t* 
   (void)faces;
   if (N <= 0 || N > 65535 || F < 0 || V < 0) return set_err(MR_EINVAL, "bad sizes");
   hipStream_t st = (hipStream_t)stream;
-  if (V > 0 && hipMemsetAsync(gverts, 0, sizeof(float) * 3 * (size_t)V, st) != hipSuccess)
-    return set_err(MR_ELAUNCH, "memset failed");
-  if (hipMemsetAsync(gviews, 0, sizeof(float) * 12 * (size_t)N, st) != hipSuccess)
-    return set_err(MR_ELAUNCH, "memset failed");
+  int rc;
+  if (V > 0 && (rc = memset_async(gverts, 0, sizeof(float) * 3 * (size_t)V, st))) return rc;
+  if ((rc = memset_async(gviews, 0, sizeof(float) * 12 * (size_t)N, st))) return rc;
   if (V == 0) return MR_OK;
   dim3 grid(ceil_div(V, 256), (unsigned)N);
-  MR_TIMED(KID_PROJECT_BWD, st, (k_project_faces_bwd<<<grid, 256, 0, st>>>(verts, V, F, ptr, adj, (const ViewRec*)views, gfv, gverts, gviews, nullptr)));
-  MR_CHECK_LAUNCH("k_project_faces_bwd");
-  return MR_OK;
+  return launch(KID_PROJECT_BWD, "k_project_faces_bwd", k_project_faces_bwd, grid, 256, 0, st, verts, V, F, ptr, adj,
+                (const ViewRec*)views, gfv, gverts, gviews, nullptr);
 }
 
 int32_t mr_project_faces_meshes_backward(const float* verts, int64_t V, const int32_t* faces, int64_t F,
@@ -608,15 +581,13 @@ int32_t mr_project_faces_meshes_backward(const float* verts, int64_t V, const in
   if (N <= 0 || N > 65535 || F < 0 || V < 0 || max_view_verts < 0) return set_err(MR_EINVAL, "bad sizes");
   if (!view_vert_first) return set_err(MR_EINVAL, "NULL argument");
   hipStream_t st = (hipStream_t)stream;
-  if (V > 0 && hipMemsetAsync(gverts, 0, sizeof(float) * 3 * (size_t)V, st) != hipSuccess)
-    return set_err(MR_ELAUNCH, "memset failed");
-  if (hipMemsetAsync(gviews, 0, sizeof(float) * 12 * (size_t)N, st) != hipSuccess)
-    return set_err(MR_ELAUNCH, "memset failed");
+  int rc;
+  if (V > 0 && (rc = memset_async(gverts, 0, sizeof(float) * 3 * (size_t)V, st))) return rc;
+  if ((rc = memset_async(gviews, 0, sizeof(float) * 12 * (size_t)N, st))) return rc;
   if (V == 0 || max_view_verts == 0) return MR_OK;
   dim3 grid(ceil_div(max_view_verts, 256), (unsigned)N);
-  MR_TIMED(KID_PROJECT_BWD, st, (k_project_faces_bwd<<<grid, 256, 0, st>>>(verts, V, F, ptr, adj, (const ViewRec*)views, gfv, gverts, gviews, view_vert_first)));
-  MR_CHECK_LAUNCH("k_project_faces_bwd");
-  return MR_OK;
+  return launch(KID_PROJECT_BWD, "k_project_faces_bwd", k_project_faces_bwd, grid, 256, 0, st, verts, V, F, ptr, adj,
+                (const ViewRec*)views, gfv, gverts, gviews, view_vert_first);
 }
 
 // The chain rule of the OpenCV pose conversion (cv_view_elem), one thread per output float.
@@ -648,19 +619,16 @@ int32_t mr_view_grads_to_opencv(const float* grad_views, int64_t N, float* grad_
                                 void* stream) {
   if (N <= 0 || N > 65535) return set_err(MR_EINVAL, "N out of range");
   if (!grad_views || !grad_R_cv || !grad_t_cv) return set_err(MR_EINVAL, "NULL argument");
-  hipStream_t st = (hipStream_t)stream;
-  k_view_grads_to_opencv<<<ceil_div(N * 12, 256), 256, 0, st>>>(grad_views, N, grad_R_cv, grad_t_cv);
-  MR_CHECK_LAUNCH("k_view_grads_to_opencv");
-  return MR_OK;
+  return launch(KID_NONE, "k_view_grads_to_opencv", k_view_grads_to_opencv, ceil_div(N * 12, 256), 256, 0, (hipStream_t)stream,
+                grad_views, N, grad_R_cv, grad_t_cv);
 }
 
 int32_t mr_vertex_normals(const float* verts, int64_t V, const int32_t* faces, int64_t F, const int32_t* ptr,
                           const int32_t* adj, float* vn, float* vraw, void* stream) {
   (void)F;
   if (V <= 0) return MR_OK;
-  MR_TIMED(KID_VNORMALS, (hipStream_t)stream, (k_vertex_normals<<<ceil_div(V, 256), 256, 0, (hipStream_t)stream>>>(verts, V, faces, ptr, adj, vn, vraw)));
-  MR_CHECK_LAUNCH("k_vertex_normals");
-  return MR_OK;
+  return launch(KID_VNORMALS, "k_vertex_normals", k_vertex_normals, ceil_div(V, 256), 256, 0, (hipStream_t)stream, verts, V,
+                faces, ptr, adj, vn, vraw);
 }
 
 static int srec_slot(const mr_shade_params_t* sp) { return (sp->out_flags >> MR_SREC_SLOT_SHIFT) & (MR_SREC_SLOTS - 1); }
@@ -818,29 +786,26 @@ static int32_t render_forward(const mr_mesh_t* m, const mr_view_t* views, int64_
              : launch_bin_view<1, 3>(SP, w, g, N, m->view_face_first, m->view_face_count, m->F, false, st, &P.S, &P);
     if (rc) return rc;
   } else {
-    if (hipMemsetAsync(w.gfix, 0, sizeof(unsigned long long) * 27 * (size_t)m->F, st) != hipSuccess ||
-        hipMemsetAsync(w.gflt, 0, sizeof(float) * 27 * (size_t)m->F, st) != hipSuccess)
-      return set_err(MR_ELAUNCH, "memset failed");
+    if ((rc = memset_async(w.gfix, 0, sizeof(unsigned long long) * 27 * (size_t)m->F, st)) ||
+        (rc = memset_async(w.gflt, 0, sizeof(float) * 27 * (size_t)m->F, st)))
+      return rc;
     if (C.R && (rc = launch_views_from_cv(C, N, st))) return rc;  // count -> scan path: the view records first
     const int64_t nzero = (int64_t)(zero_bytes(N, g, vpath) / sizeof(int));
-    MR_TIMED(KID_SETUP, st, (k_setup_zero<<<(unsigned)(vb + ceil_div(nzero, 1024)), 256, 0, st>>>(m->verts, m->V, m->faces, m->vadj_ptr, m->vadj, m->vnormals_out, m->vraw_out, vb, w.ctr, nzero)));
-    MR_CHECK_LAUNCH("k_setup_zero");
+    if ((rc = launch(KID_SETUP, "k_setup_zero", k_setup_zero, (unsigned)(vb + ceil_div(nzero, 1024)), 256, 0, st, m->verts,
+                     m->V, m->faces, m->vadj_ptr, m->vadj, m->vnormals_out, m->vraw_out, vb, w.ctr, nzero)))
+      return rc;
     const int fpt = MR_BIN_FPT;
     dim3 sgrid(ceil_div(c.maxvf, 256 * fpt), (unsigned)N);
     dim3 fgrid(ceil_div(m->F, 256 * fpt), (unsigned)N + 1);  // + the ShadeRec row (every face of the mesh(es))
     const bool lds = g.T <= MR_LDS_HIST;
     const size_t shm = lds ? sizeof(int) * (size_t)g.T : 0;
-    if (lds)
-      MR_TIMED(KID_BIN_COUNT, st, (k_bin_count_world<true><<<sgrid, 256, shm, st>>>(SP, m->verts, m->faces, m->F, (const ViewRec*)views, fpt)));
-    else
-      MR_TIMED(KID_BIN_COUNT, st, (k_bin_count_world<false><<<sgrid, 256, 0, st>>>(SP, m->verts, m->faces, m->F, (const ViewRec*)views, fpt)));
-    MR_CHECK_LAUNCH("k_bin_count_world");
+    if ((rc = launch(KID_BIN_COUNT, "k_bin_count_world", lds ? k_bin_count_world<true> : k_bin_count_world<false>, sgrid, 256,
+                     shm, st, SP, m->verts, m->faces, m->F, (const ViewRec*)views, fpt)))
+      return rc;
     if ((rc = launch_scan(w, N, g, m->view_face_count, m->F, st))) return rc;
-    if (lds)
-      MR_TIMED(KID_BIN_FILL, st, (k_bin_fill_world<true><<<fgrid, 256, shm, st>>>(SP, m->F, fpt, (int)N, P.S, (ShadeRec*)P.srec)));
-    else
-      MR_TIMED(KID_BIN_FILL, st, (k_bin_fill_world<false><<<fgrid, 256, 0, st>>>(SP, m->F, fpt, (int)N, P.S, (ShadeRec*)P.srec)));
-    MR_CHECK_LAUNCH("k_bin_fill_world");
+    if ((rc = launch(KID_BIN_FILL, "k_bin_fill_world", lds ? k_bin_fill_world<true> : k_bin_fill_world<false>, fgrid, 256, shm,
+                     st, SP, m->F, fpt, (int)N, P.S, (ShadeRec*)P.srec)))
+      return rc;
   }
   return ch4 ? launch_raster_and_shade<1, 4>(P, g, N, st, s->clip_z != 0)
              : launch_raster_and_shade<1, 3>(P, g, N, st, s->clip_z != 0);
@@ -878,7 +843,7 @@ int32_t mr_render_reshade(const mr_mesh_t* m, const mr_view_t* views, int64_t N,
                           const mr_raster_settings_t* s, const mr_shade_params_t* sp, float* depth, float* sil,
                           float* rgb, int32_t* p2f32, void* ws, size_t ws_bytes, void* stream) {
   RenderCall c;
-  const int rc = render_call(c, m, views, N, cc, ncc, s, sp, depth, sil, rgb, p2f32, ws, ws_bytes);
+  int rc = render_call(c, m, views, N, cc, ncc, s, sp, depth, sil, rgb, p2f32, ws, ws_bytes);
   if (rc) return rc;
   FwdParams& P = c.P;
   hipStream_t st = (hipStream_t)stream;
@@ -886,20 +851,32 @@ int32_t mr_render_reshade(const mr_mesh_t* m, const mr_view_t* views, int64_t N,
   if (sp->light_kind == 0 && m->vnormals_out && (sp->out_flags & MR_OUT_RGB)) {
     if (!m->vraw_out) return set_err(MR_EINVAL, "vnormals_out without vraw_out");
     P.S.vnormals = m->vnormals_out;
-    MR_TIMED(KID_VNORMALS, st, (k_vertex_normals<<<ceil_div(m->V, 256), 256, 0, st>>>(m->verts, m->V, m->faces, m->vadj_ptr, m->vadj, m->vnormals_out, m->vraw_out)));
-    MR_CHECK_LAUNCH("k_vertex_normals");
+    if ((rc = launch(KID_VNORMALS, "k_vertex_normals", k_vertex_normals, ceil_div(m->V, 256), 256, 0, st, m->verts, m->V,
+                     m->faces, m->vadj_ptr, m->vadj, m->vnormals_out, m->vraw_out)))
+      return rc;
   }
-  MR_TIMED(KID_SHADE_REC, st, (k_shade_rec<<<ceil_div(m->F, 256), 256, 0, st>>>(P.S, m->F, (ShadeRec*)P.srec)));
-  MR_CHECK_LAUNCH("k_shade_rec");
+  if ((rc = launch(KID_SHADE_REC, "k_shade_rec", k_shade_rec, ceil_div(m->F, 256), 256, 0, st, P.S, m->F, (ShadeRec*)P.srec)))
+    return rc;
   const int64_t slots_cap = N * (int64_t)c.g.T;
   return sp->rgb_channels == 4 ? launch_fill_and_shade<4>(P, slots_cap, st) : launch_fill_and_shade<3>(P, slots_cap, st);
 }
 
+// The fused backward's own workspace (its per-face totals live in the forward's).
+struct RenderBwdWS {
+  float* gnu;      // (V, 3) gradient of the raw vertex normals
+  float* rt_part;  // (N*T, 12) per-slot R/T partials
+  size_t bytes;
+};
+static RenderBwdWS carve_render_bwd(void* base, int64_t V, int64_t NT) {
+  RenderBwdWS w;
+  Carver c(base);
+  w.gnu = c.take<float>(3 * (size_t)V);
+  w.rt_part = c.take<float>(12 * (size_t)NT);
+  w.bytes = c.off;
+  return w;
+}
 size_t mr_render_backward_workspace(int64_t N, int64_t V, int64_t F, int32_t H, int32_t W) {
-  const int64_t NT = N * (int64_t)ceil_div(W, MR_TS) * ceil_div(H, MR_TS);
-  size_t off = align_up(sizeof(float) * 3 * (size_t)V, 256);                   // gnu
-  off = align_up(off + sizeof(float) * 12 * (size_t)NT, 256);                  // rt_part
-  return off;
+  return carve_render_bwd(nullptr, V, N * (int64_t)ceil_div(W, MR_TS) * ceil_div(H, MR_TS)).bytes;
 }
 
 // gviews, or gRcv and gtcv: the pose gradients as view-record rows or in the OpenCV convention
@@ -918,25 +895,23 @@ static int32_t render_backward(const mr_mesh_t* m, const float* vraw, const mr_v
   if (m->F * 27 >= (1ll << 30)) return set_err(MR_EUNSUPPORTED, "F >= 2^30 / 27 faces");  // 32-bit row offsets
   if (!fws || !bws || !gverts || (!gviews && !(gRcv && gtcv))) return set_err(MR_EINVAL, "NULL argument");
   if (sp->light_kind == 0 && !vraw) return set_err(MR_EINVAL, "raw vertex normals required");
-  const size_t need = mr_render_backward_workspace(N, m->V, m->F, s->H, s->W);
-  if (bws_bytes < need) return set_err(MR_EWORKSPACE, "backward workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const bool multi = m->view_face_first != nullptr;  // distinct meshes: record id = union face id
   const int64_t NF = multi ? m->F : N * m->F;
   BinGeom g = bin_geom(s->H, s->W, N, NF, s->max_faces_per_bin);
+  const int64_t NT = N * (int64_t)g.T;
+  const RenderBwdWS bw = carve_render_bwd(bws, m->V, NT);
+  if (bws_bytes < bw.bytes) return set_err(MR_EWORKSPACE, "backward workspace too small");
   RasterWS w = carve_raster_ws((void*)fws, N, NF, g, m->F);
   const bool vcol = m->tex_kind == 1;
   const int ACC = vcol ? 27 : 18;
-  const int64_t NT = N * (int64_t)g.T;
-  float* gnu = (float*)bws;
-  float* rt_part = (float*)((char*)bws + align_up(sizeof(float) * 3 * (size_t)m->V, 256));
   // the per-face totals (fixed point + float remainder) live in the forward's workspace, which the
   // forward cleared; a second backward over the same forward (MR_GRAD_ROWS_CLEARED not set) clears
   // them again
   if (!(sp->out_flags & MR_GRAD_ROWS_CLEARED) &&
-      (hipMemsetAsync(w.gfix, 0, sizeof(unsigned long long) * ACC * (size_t)m->F, st) != hipSuccess ||
-       hipMemsetAsync(w.gflt, 0, sizeof(float) * ACC * (size_t)m->F, st) != hipSuccess))
-    return set_err(MR_ELAUNCH, "memset failed");
+      ((rc = memset_async(w.gfix, 0, sizeof(unsigned long long) * ACC * (size_t)m->F, st)) ||
+       (rc = memset_async(w.gflt, 0, sizeof(float) * ACC * (size_t)m->F, st))))
+    return rc;
   RenderBwdParams P;
   memset(&P, 0, sizeof(P));
   P.N = (int)N; P.H = s->H; P.W = s->W; P.TX = g.TX; P.T = g.T;
@@ -962,7 +937,7 @@ static int32_t render_backward(const mr_mesh_t* m, const float* vraw, const mr_v
   P.gfix = w.gfix;
   P.gface = w.gflt;
   P.fflag = w.ctr + CTR_FLT;
-  P.rt_part = rt_part;
+  P.rt_part = bw.rt_part;
   P.frec = w.frec;
   P.sgrp = w.sgrp;
   P.sgpix = w.sgpix;
@@ -986,13 +961,13 @@ static int32_t render_backward(const mr_mesh_t* m, const float* vraw, const mr_v
   }
   if (rc) return rc;
   VertexGradArgs A;
-  A.RR.part = rt_part; A.RR.vslot = w.vslot; A.RR.N = (int)N;
+  A.RR.part = bw.rt_part; A.RR.vslot = w.vslot; A.RR.N = (int)N;
   // the forward's slot ranges: one per (view, band) on the per-view binning, one per view otherwise
   A.RR.bands = view_binning(g, N, NF) ? bin_bands(N, g) : 1;
   A.RR.gviews = gviews; A.RR.gRcv = gRcv; A.RR.gtcv = gtcv;
   A.m = m; A.gfix = w.gfix; A.gface = w.gflt; A.fflag = P.fflag;
   A.vraw = sp->light_kind == 0 ? vraw : nullptr;
-  A.gnu = gnu; A.gverts = gverts; A.gcol = gcol;
+  A.gnu = bw.gnu; A.gverts = gverts; A.gcol = gcol;
   A.timed = true;
   return vcol ? launch_vertex_grads<27>(A, st) : launch_vertex_grads<18>(A, st);
 }
@@ -1059,17 +1034,25 @@ int32_t mr_shade_fragments_forward(const mr_mesh_t* m, const int64_t* p2f, const
   hipStream_t st = (hipStream_t)stream;
   FragShadeParams P = make_frag(m, sp, cc, ncc, p2f, zbuf, bary, dists, N, H, W, K, ws);
   P.rgba = rgba;
-  MR_TIMED(KID_SHADE_REC, st, (k_shade_rec<<<ceil_div(m->F, 256), 256, 0, st>>>(P.S, m->F, (ShadeRec*)ws)));
-  MR_CHECK_LAUNCH("k_shade_rec");
-  MR_TIMED(KID_FRAG_SHADE, st, (k_frag_shade_fwd<<<ceil_div(N * (int64_t)H * W, 256), 256, 0, st>>>(P)));
-  MR_CHECK_LAUNCH("k_frag_shade_fwd");
-  return MR_OK;
+  if ((rc = launch(KID_SHADE_REC, "k_shade_rec", k_shade_rec, ceil_div(m->F, 256), 256, 0, st, P.S, m->F, (ShadeRec*)ws)))
+    return rc;
+  return launch(KID_FRAG_SHADE, "k_frag_shade_fwd", k_frag_shade_fwd, ceil_div(N * (int64_t)H * W, 256), 256, 0, st, P);
 }
 
-size_t mr_shade_fragments_backward_workspace(int64_t V, int64_t F) {
-  size_t off = align_up(sizeof(float) * 27 * (size_t)(F > 0 ? F : 1), 256);  // gface
-  return align_up(off + sizeof(float) * 3 * (size_t)(V > 0 ? V : 1), 256);    // gnu
+struct FragBwdWS {
+  float* gface;  // (F, 27) per-face gradient totals (float rows)
+  float* gnu;    // (V, 3) gradient of the raw vertex normals
+  size_t bytes;
+};
+static FragBwdWS carve_frag_bwd(void* base, int64_t V, int64_t F) {
+  FragBwdWS w;
+  Carver c(base);
+  w.gface = c.take<float>(27 * (size_t)(F > 0 ? F : 1));
+  w.gnu = c.take<float>(3 * (size_t)(V > 0 ? V : 1));
+  w.bytes = c.off;
+  return w;
 }
+size_t mr_shade_fragments_backward_workspace(int64_t V, int64_t F) { return carve_frag_bwd(nullptr, V, F).bytes; }
 
 int32_t mr_shade_fragments_backward(const mr_mesh_t* m, const float* vraw, const int64_t* p2f, const float* zbuf,
                                     const float* bary, const float* dists, int64_t N, int32_t H, int32_t W,
@@ -1083,45 +1066,44 @@ int32_t mr_shade_fragments_backward(const mr_mesh_t* m, const float* vraw, const
   if (!grad_rgba || !fwd_ws || !bws || !g_verts || (!g_zbuf && !sil && !hard) || (!g_bary && !sil) ||
       (!g_dists && !hard))
     return set_err(MR_EINVAL, "NULL argument");
-  if (bws_bytes < mr_shade_fragments_backward_workspace(m->V, m->F)) return set_err(MR_EWORKSPACE, "backward workspace too small");
+  const FragBwdWS bw = carve_frag_bwd(bws, m->V, m->F);
+  if (bws_bytes < bw.bytes) return set_err(MR_EWORKSPACE, "backward workspace too small");
   if (sp->light_kind == 0 && !vraw) return set_err(MR_EINVAL, "raw vertex normals required");
   hipStream_t st = (hipStream_t)stream;
   const bool vcol = m->tex_kind == 1;
   const int ACC = vcol ? 27 : 18;
-  float* gface = (float*)bws;
-  float* gnu = (float*)((char*)bws + align_up(sizeof(float) * 27 * (size_t)m->F, 256));
-  if (hipMemsetAsync(gface, 0, sizeof(float) * ACC * (size_t)m->F, st) != hipSuccess) return set_err(MR_ELAUNCH, "memset failed");
+  if ((rc = memset_async(bw.gface, 0, sizeof(float) * ACC * (size_t)m->F, st))) return rc;
   if (g_tex_rgba && m->tex_kind == 2 &&
-      hipMemsetAsync(g_tex_rgba, 0, sizeof(float) * 4 * (size_t)m->tex_h * m->tex_w, st) != hipSuccess)
-    return set_err(MR_ELAUNCH, "memset failed");
+      (rc = memset_async(g_tex_rgba, 0, sizeof(float) * 4 * (size_t)m->tex_h * m->tex_w, st)))
+    return rc;
   if (g_verts_uvs && m->tex_kind == 2 && num_verts_uvs > 0 &&
-      hipMemsetAsync(g_verts_uvs, 0, sizeof(float) * 2 * (size_t)num_verts_uvs, st) != hipSuccess)
-    return set_err(MR_ELAUNCH, "memset failed");
+      (rc = memset_async(g_verts_uvs, 0, sizeof(float) * 2 * (size_t)num_verts_uvs, st)))
+    return rc;
   FragShadeParams P = make_frag(m, sp, cc, ncc, p2f, zbuf, bary, dists, N, H, W, K, fwd_ws);
   P.g_rgba = grad_rgba;
   P.g_zbuf = g_zbuf; P.g_bary = g_bary; P.g_dists = g_dists;
-  P.gface = gface;
+  P.gface = bw.gface;
   P.gmap = m->tex_kind == 2 ? g_tex_rgba : nullptr;
   P.guv = m->tex_kind == 2 ? g_verts_uvs : nullptr;
   const int grid = ceil_div(N * (int64_t)H * W, 256);
   {  // the fragment gradients of empty slots are zero: cleared here with coalesced fills
     const size_t slots = (size_t)N * H * W * K;
-    if ((g_zbuf && hipMemsetAsync(g_zbuf, 0, sizeof(float) * slots, st) != hipSuccess) ||
-        (g_dists && hipMemsetAsync(g_dists, 0, sizeof(float) * slots, st) != hipSuccess) ||
-        (g_bary && hipMemsetAsync(g_bary, 0, sizeof(float) * 3 * slots, st) != hipSuccess))
-      return set_err(MR_ELAUNCH, "memset failed");
+    if ((g_zbuf && (rc = memset_async(g_zbuf, 0, sizeof(float) * slots, st))) ||
+        (g_dists && (rc = memset_async(g_dists, 0, sizeof(float) * slots, st))) ||
+        (g_bary && (rc = memset_async(g_bary, 0, sizeof(float) * 3 * slots, st))))
+      return rc;
   }
-  if (vcol) MR_TIMED(KID_FRAG_SHADE_BWD, st, (k_frag_shade_bwd<27><<<grid, 256, 0, st>>>(P)));
-  else MR_TIMED(KID_FRAG_SHADE_BWD, st, (k_frag_shade_bwd<18><<<grid, 256, 0, st>>>(P)));
-  MR_CHECK_LAUNCH("k_frag_shade_bwd");
+  if ((rc = launch(KID_FRAG_SHADE_BWD, "k_frag_shade_bwd", vcol ? k_frag_shade_bwd<27> : k_frag_shade_bwd<18>, grid, 256, 0, st,
+                   P)))
+    return rc;
   // vertex gradients of the attribute rows (interpolated positions and normals, vertex colours): float rows
   // only, no views to reduce, not timed
   VertexGradArgs A;
   memset(&A, 0, sizeof(A));
   A.RR.bands = 1;
-  A.m = m; A.gface = gface;
+  A.m = m; A.gface = bw.gface;
   A.vraw = (sp->light_kind == 0 && !P.sil) ? vraw : nullptr;
-  A.gnu = gnu; A.gverts = g_verts; A.gcol = g_vcolors;
+  A.gnu = bw.gnu; A.gverts = g_verts; A.gcol = g_vcolors;
   return vcol ? launch_vertex_grads<27>(A, st) : launch_vertex_grads<18>(A, st);
 }
 
@@ -1143,9 +1125,10 @@ int32_t mr_workspace_stats(const void* ws, int64_t N, int64_t Ftot, int32_t H, i
   BinGeom g = bin_geom(H, W, N, Ftot > 0 ? Ftot : 1, mfpb);
   RasterWS w = carve_raster_ws((void*)ws, N, Ftot > 0 ? Ftot : 1, g);
   const size_t n = (size_t)N + CTR_COUNT + (size_t)N * g.T;  // ctr, cnt and vtot are contiguous
-  if (hipMemsetAsync(w.ctr + CTR_COVERED, 0, sizeof(int), st) != hipSuccess) return set_err(MR_ELAUNCH, "memset failed");
-  k_count_covered<<<1024, 256, 0, st>>>(w.sface, w.ctr, w.ctr + CTR_COVERED);
-  MR_CHECK_LAUNCH("k_count_covered");
+  int rc;
+  if ((rc = memset_async(w.ctr + CTR_COVERED, 0, sizeof(int), st))) return rc;
+  if ((rc = launch(KID_NONE, "k_count_covered", k_count_covered, 1024, 256, 0, st, w.sface, w.ctr, w.ctr + CTR_COVERED)))
+    return rc;
   int* h = (int*)malloc(sizeof(int) * n);
   if (!h) return set_err(MR_EINVAL, "out of host memory");
   if (hipMemcpyAsync(h, w.ctr, sizeof(int) * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -1259,18 +1242,13 @@ struct LossWS {
 static LossWS carve_loss(void* ws, int64_t npix) {
   const size_t nb = (size_t)std::max<int64_t>(ceil_div(npix, 256 * MR_LOSS_PPT), 1);
   LossWS w;
-  char* b = (char*)ws;
-  size_t off = 0;
-  w.part = (float*)(b + off);
-  off = align_up(off + sizeof(float) * 3 * nb, 256);
-  w.pcnt = (int*)(b + off);
-  off = align_up(off + sizeof(int) * nb, 256);
-  w.count = (int64_t*)(b + off);
+  Carver c(ws);
+  w.part = c.take<float>(3 * nb);
+  w.pcnt = c.take<int>(nb);
+  w.count = c.take<int64_t>(2);
   w.mtot = w.count + 1;
-  off = align_up(off + 2 * sizeof(int64_t), 256);
-  w.mcnt = (int*)(b + off);
-  off = align_up(off + sizeof(int) * MR_LOSS_BLOCKS, 256);
-  w.bytes = off;
+  w.mcnt = c.take<int>(MR_LOSS_BLOCKS);
+  w.bytes = c.off;
   return w;
 }
 
@@ -1284,20 +1262,18 @@ static int32_t pose_loss_run(const PoseLossParams& P, float* total, float* terms
   const int64_t nb = ceil_div(P.npix, 256 * MR_LOSS_PPT);
   if (nb >= (1ll << 31)) return set_err(MR_EUNSUPPORTED, "npix too large");
   const bool grads = g_depth != nullptr;
+  int rc;
   if (grads) {
     const int nm = (int)std::min<int64_t>(MR_LOSS_BLOCKS, ceil_div(P.npix, 256));
-    k_mask_count<<<nm, 256, 0, st>>>(P.mask, P.npix, w.mcnt);
-    MR_CHECK_LAUNCH("k_mask_count");
-    k_mask_total<<<1, 256, 0, st>>>(w.mcnt, nm, w.mtot);
-    MR_CHECK_LAUNCH("k_mask_total");
-    MR_TIMED(KID_POSE_LOSS, st, (k_pose_loss_fused<true><<<(unsigned)nb, 256, 0, st>>>(P, w.mtot, w.part, w.pcnt, g_depth, g_sil, g_rgb)));
-  } else {
-    MR_TIMED(KID_POSE_LOSS, st, (k_pose_loss_fused<false><<<(unsigned)nb, 256, 0, st>>>(P, w.mtot, w.part, w.pcnt, nullptr, nullptr, nullptr)));
+    if ((rc = launch(KID_NONE, "k_mask_count", k_mask_count, nm, 256, 0, st, P.mask, P.npix, w.mcnt))) return rc;
+    if ((rc = launch(KID_NONE, "k_mask_total", k_mask_total, 1, 256, 0, st, w.mcnt, nm, w.mtot))) return rc;
   }
-  MR_CHECK_LAUNCH("k_pose_loss_fused");
-  k_pose_loss_final<<<1, 1024, 0, st>>>(P, w.part, w.pcnt, (int)nb, total, terms, w.count);
-  MR_CHECK_LAUNCH("k_pose_loss_final");
-  return MR_OK;
+  // (the callers pass all three gradient buffers or none)
+  if ((rc = launch(KID_POSE_LOSS, "k_pose_loss_fused", grads ? k_pose_loss_fused<true> : k_pose_loss_fused<false>, (unsigned)nb,
+                   256, 0, st, P, w.mtot, w.part, w.pcnt, g_depth, g_sil, g_rgb)))
+    return rc;
+  return launch(KID_NONE, "k_pose_loss_final", k_pose_loss_final, 1, 1024, 0, st, P, w.part, w.pcnt, (int)nb, total, terms,
+                w.count);
 }
 
 int32_t mr_pose_loss_forward(const float* depth, const float* sil, int64_t sil_stride, const float* rgb,
@@ -1336,11 +1312,8 @@ int32_t mr_pose_loss_scale(const float* g_total, int64_t npix, int64_t sil_strid
   if (!g_total || !g_depth || !g_sil || !g_rgb) return set_err(MR_EINVAL, "NULL argument");
   if ((sil_stride != 1 && sil_stride != 4) || (rgb_stride != 3 && rgb_stride != 4))
     return set_err(MR_EINVAL, "bad strides");
-  hipStream_t st = (hipStream_t)stream;
-  MR_TIMED(KID_POSE_LOSS_SCALE, st, (k_pose_loss_scale<<<1024, 256, 0, st>>>(g_total, npix, npix * sil_stride, npix * rgb_stride,
-                                                                             g_depth, g_sil, g_rgb)));
-  MR_CHECK_LAUNCH("k_pose_loss_scale");
-  return MR_OK;
+  return launch(KID_POSE_LOSS_SCALE, "k_pose_loss_scale", k_pose_loss_scale, 1024, 256, 0, (hipStream_t)stream, g_total, npix,
+                npix * sil_stride, npix * rgb_stride, g_depth, g_sil, g_rgb);
 }
 
 int32_t mr_pose_loss_backward(const float* depth, const float* sil, int64_t sil_stride, const float* rgb,
@@ -1354,18 +1327,15 @@ int32_t mr_pose_loss_backward(const float* depth, const float* sil, int64_t sil_
   const int64_t* count = carve_loss((void*)fwd_ws, npix).count;
   if ((sil_stride == 4 && ((uintptr_t)g_sil & 15)) || (rgb_stride == 4 && ((uintptr_t)g_rgb & 15)))
     return set_err(MR_EINVAL, "RGBA gradient buffers must be 16-byte aligned");
-  k_pose_loss_bwd<<<(unsigned)ceil_div(npix, 256), 256, 0, (hipStream_t)stream>>>(P, g_total, count, g_depth, g_sil, g_rgb);
-  MR_CHECK_LAUNCH("k_pose_loss_bwd");
-  return MR_OK;
+  return launch(KID_NONE, "k_pose_loss_bwd", k_pose_loss_bwd, (unsigned)ceil_div(npix, 256), 256, 0, (hipStream_t)stream, P,
+                g_total, count, g_depth, g_sil, g_rgb);
 }
 
 int32_t mr_quaternion_to_matrix(const float* q, int64_t q_stride, int64_t N, float* R, void* stream) {
   if (N < 0 || q_stride < 4) return set_err(MR_EINVAL, "bad quaternion batch");
   if (N == 0) return MR_OK;
   if (!q || !R) return set_err(MR_EINVAL, "NULL argument");
-  k_quat_to_matrix<<<ceil_div(N, 256), 256, 0, (hipStream_t)stream>>>(q, q_stride, N, R);
-  MR_CHECK_LAUNCH("k_quat_to_matrix");
-  return MR_OK;
+  return launch(KID_NONE, "k_quat_to_matrix", k_quat_to_matrix, ceil_div(N, 256), 256, 0, (hipStream_t)stream, q, q_stride, N, R);
 }
 
 int32_t mr_quaternion_to_matrix_backward(const float* q, int64_t q_stride, const float* gR, int64_t N, float* gq,
@@ -1373,9 +1343,8 @@ int32_t mr_quaternion_to_matrix_backward(const float* q, int64_t q_stride, const
   if (N < 0 || q_stride < 4) return set_err(MR_EINVAL, "bad quaternion batch");
   if (N == 0) return MR_OK;
   if (!q || !gR || !gq) return set_err(MR_EINVAL, "NULL argument");
-  k_quat_to_matrix_bwd<<<ceil_div(N, 256), 256, 0, (hipStream_t)stream>>>(q, q_stride, gR, N, gq);
-  MR_CHECK_LAUNCH("k_quat_to_matrix_bwd");
-  return MR_OK;
+  return launch(KID_NONE, "k_quat_to_matrix_bwd", k_quat_to_matrix_bwd, ceil_div(N, 256), 256, 0, (hipStream_t)stream, q,
+                q_stride, gR, N, gq);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
-// mi355r — Host-side runtime of the library: error state, per-kernel timing events, the workspace
-// carve (face records, tile lists, work units, per-slot winners) and its counters.
-// Part of the single translation unit mr_raster.hip (included there, in this order).
+// mi355r — The raster's workspace: batch geometry, the carve (face records, tile lists, work units, per-slot
+// winners) and its counters. The host runtime every translation unit shares is mr_host.h.
+// Part of mr_raster.hip (included there, in this order).
 #pragma once
 
 #define MR_TS 8         // raster tile edge: one 64-lane wave per 8x8 tile (lane = pixel)
@@ -8,72 +8,6 @@
 #define MR_HT 512       // LDS hash slots in the backward
 #define MR_BIN_FPT 2     // faces per thread in the world-space binning kernels
 #define MR_LDS_HIST 16384  // per-view tiles binned through an LDS histogram (else global atomics)
-
-static thread_local char g_err[512];
-static int set_err(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-#define MR_CHECK_LAUNCH(name)                                                         \
-  do {                                                                                \
-    hipError_t _e = hipGetLastError();                                                \
-    if (_e != hipSuccess) return set_err(MR_ELAUNCH, "%s: %s", name, hipGetErrorString(_e)); \
-  } while (0)
-
-// ---------------------------------------------------------------------------
-// Optional per-kernel timing: HIP events recorded on the launch stream around
-// every kernel while enabled (bench.py reads them to price the dominant kernel).
-// ---------------------------------------------------------------------------
-enum KernelId { KID_BIN_COUNT, KID_BIN_SCAN, KID_BIN_FILL, KID_TILE_RASTER, KID_SHADE_FRAG, KID_SHADE_RENDER, KID_RASTER_BWD, KID_RT_VGRAD_B, KID_BWD_GEOM, KID_RT_REDUCE,
-                KID_VGRAD_A, KID_VGRAD_B,
-                KID_VNORMALS, KID_PROJECT, KID_PROJECT_BWD, KID_SHADE_REC, KID_FILL_FRAG,
-                KID_RASTER_K, KID_BWD_FUSED, KID_RT_VGRAD_A, KID_FRAG_SHADE, KID_FRAG_SHADE_BWD, KID_SETUP, KID_BIN_RECT, KID_BIN_VIEW,
-                KID_FACE_REDUCE, KID_BAND_BUCKET, KID_POSE_LOSS, KID_POSE_LOSS_SCALE, KID_UNIT_ORDER, KID_COUNT };
-static const char* kKernelNames[KID_COUNT] = {"k_bin_count", "k_bin_scan", "k_bin_fill", "k_tile_raster",
-                                              "k_shade<0>", "k_shade<1>",
-                                              "k_raster_bwd", "k_rt_vgrad_b", "k_bwd_geom(unused)", "k_rt_reduce",
-                                              "k_vgrad_a", "k_vgrad_b",
-                                              "k_vertex_normals", "k_project_faces", "k_project_faces_bwd",
-                                              "k_shade_rec", "k_fill<0>", "k_raster_k", "k_bwd_fused",
-                                              "k_rt_vgrad_a", "k_frag_shade_fwd", "k_frag_shade_bwd", "k_setup_zero",
-                                              "k_bin_rect", "k_bin_view", "k_face_reduce(unused)", "k_band_bucket",
-                                              "k_pose_loss_fused", "k_pose_loss_scale", "k_unit_order"};
-#define MR_TPOOL 4096
-static struct {
-  int enabled;
-  int created;
-  hipEvent_t ev[2 * MR_TPOOL];
-  int kid[MR_TPOOL];
-  int used;
-  int dropped;
-} g_t;
-
-static int timing_begin(hipStream_t st) {
-  if (!g_t.enabled || g_t.used >= MR_TPOOL) {
-    if (g_t.enabled) g_t.dropped++;
-    return -1;
-  }
-  const int i = g_t.used++;
-  (void)hipEventRecord(g_t.ev[2 * i], st);
-  return i;
-}
-static void timing_end(int i, int kid, hipStream_t st) {
-  if (i < 0) return;
-  g_t.kid[i] = kid;
-  (void)hipEventRecord(g_t.ev[2 * i + 1], st);
-}
-#define MR_TIMED(kid, st, launch)              \
-  do {                                         \
-    const int _ti = timing_begin(st);          \
-    launch;                                    \
-    timing_end(_ti, kid, st);                  \
-  } while (0)
-
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-static inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // ---------------------------------------------------------------------------
 // Workspace: face records, per-(view, 8x8 tile) face lists (count -> scan ->
@@ -181,65 +115,41 @@ struct RasterWS {
 };
 static RasterWS carve_raster_ws(void* base, int64_t N, int64_t Ftot, const BinGeom& g, int64_t Fshade = 0) {
   RasterWS w;
-  size_t off = 0;
-  char* b = (char*)base;
-  const size_t NT = (size_t)N * g.T;
+  Carver c(base);
+  const size_t NT = (size_t)N * g.T, Fr = 2 * (size_t)(Ftot > 0 ? Ftot : 1), Fs = (size_t)Fshade;
+  const size_t px = Fshade > 0 ? 64 * NT : 0;  // slot pixels of the fused path
   // face records: [0, Ftot) one per face instance, [Ftot, 2 Ftot) the second triangle of a face
   // split at the near plane (only written for such faces)
-  w.recs = (FaceRec*)(b + off);
-  off = align_up(off + sizeof(FaceRec) * 2 * (size_t)(Ftot > 0 ? Ftot : 1), 256);
-  w.ctr = (int*)(b + off);  // 256-B aligned: the u64 entry counter at ctr + CTR_ENTRIES64
+  w.recs = c.take<FaceRec>(Fr);
+  w.ctr = c.take<int>(NT + (size_t)N + CTR_COUNT);  // 256-B aligned: the u64 entry counter at ctr + CTR_ENTRIES64
   w.cnt = w.ctr + CTR_COUNT;
   w.vtot = w.cnt + NT;
-  off = align_up(off + sizeof(int) * (NT + (size_t)N + CTR_COUNT), 256);
-  w.rects = (uint32_t*)(b + off);
-  off = align_up(off + sizeof(uint32_t) * 2 * (size_t)(Ftot > 0 ? Ftot : 1), 256);
-  w.start = (int*)(b + off);
-  off = align_up(off + sizeof(int) * NT, 256);
-  w.cur = (int*)(b + off);
-  off = align_up(off + sizeof(int) * NT, 256);
-  w.vbase = (int*)(b + off);
-  off = align_up(off + sizeof(int) * (size_t)N, 256);
-  w.tdone = (int*)(b + off);
-  off = align_up(off + sizeof(int) * NT, 256);
-  w.vslot = (int*)(b + off);
-  off = align_up(off + sizeof(int) * 2 * MR_BANDS_MAX * (size_t)N, 256);
-  w.stile = (int*)(b + off);
-  off = align_up(off + sizeof(int) * NT, 256);
-  w.units = (int4*)(b + off);
-  off = align_up(off + sizeof(int4) * (size_t)g.unit_cap, 256);
-  w.units2 = (int4*)(b + off);  // the units in the raster's order (k_unit_order)
-  off = align_up(off + sizeof(int4) * (size_t)g.unit_cap, 256);
-  w.list = (int*)(b + off);
-  off = align_up(off + sizeof(int) * (size_t)g.list_cap, 256);
-  w.tkey = (unsigned long long*)(b + off);
-  off = align_up(off + sizeof(unsigned long long) * 64 * NT, 256);
-  w.sface = (int*)(b + off);
-  off = align_up(off + sizeof(int) * 64 * NT, 256);
-  w.srec = (ShadeRec*)(b + off);  // MR_SREC_SLOTS slots of Fshade records (mr_render_reshade)
-  off = align_up(off + sizeof(ShadeRec) * MR_SREC_SLOTS * (size_t)Fshade, 256);
-  w.sorder = (int*)(b + off);  // the K-deep raster's slot order (k_slot_order)
-  off = align_up(off + sizeof(int) * (size_t)NT, 256);
-  w.gfix = (unsigned long long*)(b + off);
-  off = align_up(off + sizeof(unsigned long long) * 27 * (size_t)Fshade, 256);
-  w.gflt = (float*)(b + off);
-  off = align_up(off + sizeof(float) * 27 * (size_t)Fshade, 256);
-  w.frec = (float4*)(b + off);
-  off = align_up(off + sizeof(float4) * (Fshade > 0 ? 64 * NT : 0), 256);
-  w.sgrp = (int*)(b + off);
-  off = align_up(off + sizeof(int) * (Fshade > 0 ? 64 * NT : 0), 256);
-  w.sgpix = (uint8_t*)(b + off);
-  off = align_up(off + (Fshade > 0 ? 64 * NT : 0), 256);
-  w.crec = (ClipRec*)(b + off);
-  off = align_up(off + sizeof(ClipRec) * 2 * (size_t)(Ftot > 0 ? Ftot : 1), 256);
+  w.rects = c.take<uint32_t>(Fr);
+  w.start = c.take<int>(NT);
+  w.cur = c.take<int>(NT);
+  w.vbase = c.take<int>((size_t)N);
+  w.tdone = c.take<int>(NT);
+  w.vslot = c.take<int>(2 * MR_BANDS_MAX * (size_t)N);
+  w.stile = c.take<int>(NT);
+  w.units = c.take<int4>((size_t)g.unit_cap);
+  w.units2 = c.take<int4>((size_t)g.unit_cap);  // the units in the raster's order (k_unit_order)
+  w.list = c.take<int>((size_t)g.list_cap);
+  w.tkey = c.take<unsigned long long>(64 * NT);
+  w.sface = c.take<int>(64 * NT);
+  w.srec = c.take<ShadeRec>(MR_SREC_SLOTS * Fs);  // MR_SREC_SLOTS slots of Fshade records (mr_render_reshade)
+  w.sorder = c.take<int>(NT);  // the K-deep raster's slot order (k_slot_order)
+  w.gfix = c.take<unsigned long long>(27 * Fs);
+  w.gflt = c.take<float>(27 * Fs);
+  w.frec = c.take<float4>(px);
+  w.sgrp = c.take<int>(px);
+  w.sgpix = c.take<uint8_t>(px);
+  w.crec = c.take<ClipRec>(Fr);
   const int B = bin_bands(N, g);
   w.nbcnt = B > 1 ? (int)(N * B) : 0;
   w.bcap = B > 1 ? 2 * ((Ftot > 0 ? Ftot : 1) + N - 1) / N : 0;
-  w.bcnt = (int*)(b + off);
-  off = align_up(off + sizeof(int) * (size_t)w.nbcnt, 256);
-  w.blist = (int*)(b + off);
-  off = align_up(off + sizeof(int) * (size_t)w.nbcnt * (size_t)w.bcap, 256);
-  w.bytes = off;
+  w.bcnt = c.take<int>((size_t)w.nbcnt);
+  w.blist = c.take<int>((size_t)w.nbcnt * (size_t)w.bcap);
+  w.bytes = c.off;
   return w;
 }
 // Bytes to clear from w.ctr before a forward: the counters and, on the count -> scan path, the

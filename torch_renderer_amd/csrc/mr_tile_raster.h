@@ -1149,10 +1149,7 @@ static int launch_shade_render(const FwdParams& P, int64_t slots_cap, hipStream_
   const bool spec = drop_in_shading(P.S, CH, P.out_flags) && !P.p2f32 &&
                     P.out_flags == (MR_OUT_DEPTH | MR_OUT_SIL | MR_OUT_RGB);
   const int sg = shade_grid(slots_cap, spec ? g1 : g0);
-  if (spec) MR_TIMED(KID_SHADE_RENDER, st, (k_shade_render<CH, 1><<<sg, 256, 0, st>>>(P)));
-  else MR_TIMED(KID_SHADE_RENDER, st, (k_shade_render<CH, 0><<<sg, 256, 0, st>>>(P)));
-  MR_CHECK_LAUNCH("k_shade_render");
-  return MR_OK;
+  return launch(KID_SHADE_RENDER, "k_shade_render", spec ? k_shade_render<CH, 1> : k_shade_render<CH, 0>, sg, 256, 0, st, P);
 }
 
 // Raster (+ background) then covered-pixel outputs; grids sized once per kernel instance.
@@ -1168,19 +1165,17 @@ static int launch_raster_and_shade(FwdParams P, const BinGeom& g, int64_t N, hip
   // and only for batches of MR_UNIT_ORDER_MIN_VIEWS views or more: C5's single view rasters 0.3 us slower without it
   // and saves the 4.4-us launch, profiles/r6n_c5_ab.txt)
   if (MR_UNIT_ORDER && MODE == 1 && P.units_ws2 && N >= MR_UNIT_ORDER_MIN_VIEWS) {
-    MR_TIMED(KID_UNIT_ORDER, st, (k_unit_order<<<8, 1024, 0, st>>>(P.units, P.ctr, P.units_ws2)));
-    MR_CHECK_LAUNCH("k_unit_order");
+    if (int rc = launch(KID_UNIT_ORDER, "k_unit_order", k_unit_order, 8, 1024, 0, st, P.units, P.ctr, P.units_ws2)) return rc;
     P.units = P.units_ws2;
   }
-  if (clip) MR_TIMED(KID_TILE_RASTER, st, (k_tile_raster<MODE, CH, true><<<rgrid_c, 256, 0, st>>>(P)));
-  else MR_TIMED(KID_TILE_RASTER, st, (k_tile_raster<MODE, CH, false><<<rgrid, 256, 0, st>>>(P)));
-  MR_CHECK_LAUNCH("k_tile_raster");
+  if (int rc = launch(KID_TILE_RASTER, "k_tile_raster", clip ? k_tile_raster<MODE, CH, true> : k_tile_raster<MODE, CH, false>,
+                      clip ? rgrid_c : rgrid, 256, 0, st, P))
+    return rc;
   if (MODE == 0 && P.emit_frag) return MR_OK;  // the raster wrote the listed tiles' fragments
   const int64_t slots_cap = N * (int64_t)g.T;
   if (MODE == 1 && MR_SHADE_RENDER) return launch_shade_render<CH>(P, slots_cap, st);
-  MR_TIMED(MODE == 0 ? KID_SHADE_FRAG : KID_SHADE_RENDER, st, (k_shade<MODE, CH><<<shade_grid(slots_cap, sgrid), 256, 0, st>>>(P)));
-  MR_CHECK_LAUNCH("k_shade");
-  return MR_OK;
+  return launch(MODE == 0 ? KID_SHADE_FRAG : KID_SHADE_RENDER, "k_shade", k_shade<MODE, CH>, shade_grid(slots_cap, sgrid), 256, 0,
+                st, P);
 }
 
 // A reshade (mr_render_reshade) over a forward's stored winners: every pixel's background, then the covered pixels.
@@ -1189,9 +1184,6 @@ static int launch_fill_and_shade(const FwdParams& P, int64_t slots_cap, hipStrea
   static int fgrid = 0, sgrid = 0;
   if (!fgrid) fgrid = resident_grid(k_fill<1, CH>, 256, 8);
   if (!sgrid) sgrid = resident_grid(k_shade<1, CH>, 256, 6);
-  MR_TIMED(KID_FILL_FRAG, st, (k_fill<1, CH><<<fgrid, 256, 0, st>>>(P)));
-  MR_CHECK_LAUNCH("k_fill");
-  MR_TIMED(KID_SHADE_RENDER, st, (k_shade<1, CH><<<shade_grid(slots_cap, sgrid), 256, 0, st>>>(P)));
-  MR_CHECK_LAUNCH("k_shade");
-  return MR_OK;
+  if (int rc = launch(KID_FILL_FRAG, "k_fill", k_fill<1, CH>, fgrid, 256, 0, st, P)) return rc;
+  return launch(KID_SHADE_RENDER, "k_shade", k_shade<1, CH>, shade_grid(slots_cap, sgrid), 256, 0, st, P);
 }

@@ -174,29 +174,22 @@ struct VertexGradArgs {
   const float* vraw;  // NULL: no normal chain
   float* gnu;
   float *gverts, *gcol;
-  bool timed;  // MR_TIMED under KID_RT_VGRAD_A / _B, KID_VGRAD_B
+  bool timed;  // under KID_RT_VGRAD_A / _B, KID_VGRAD_B
 };
 template <int ACC>
 static int launch_vertex_grads(const VertexGradArgs& A, hipStream_t st) {
   const mr_mesh_t* m = A.m;
   const unsigned rows = (unsigned)(A.RR.N + ceil_div(m->V * MR_VL, MR_VGRAD_NT));  // views + vertex-gather workgroups
-  int ti = A.timed ? timing_begin(st) : -1;
-  if (!A.vraw && A.RR.N > 0) {
-    k_rt_vgrad_b<ACC><<<rows, MR_VGRAD_NT, 0, st>>>(A.RR, m->V, m->vadj_ptr, m->vadj, A.gfix, A.gface, A.fflag, A.gverts, A.gcol);
-    timing_end(ti, KID_RT_VGRAD_B, st);
-    MR_CHECK_LAUNCH("k_rt_vgrad_b");
-    return MR_OK;
-  }
-  if (A.vraw) {
-    k_rt_vgrad_a<ACC><<<rows, MR_VGRAD_NT, 0, st>>>(A.RR, m->V, m->vadj_ptr, m->vadj, A.gfix, A.gface, A.fflag, A.vraw, A.gnu);
-    timing_end(ti, KID_RT_VGRAD_A, st);
-    MR_CHECK_LAUNCH("k_rt_vgrad_a");
-    ti = A.timed ? timing_begin(st) : -1;
-  }
-  k_vgrad_b<ACC><<<ceil_div(m->V * MR_VL, 256), 256, 0, st>>>(m->V, m->verts, m->faces, m->vadj_ptr, m->vadj, A.gfix, A.gface, A.fflag, A.gnu, A.vraw ? 1 : 0, A.gverts, A.gcol);
-  timing_end(ti, KID_VGRAD_B, st);
-  MR_CHECK_LAUNCH("k_vgrad_b");
-  return MR_OK;
+  if (!A.vraw && A.RR.N > 0)
+    return launch(A.timed ? KID_RT_VGRAD_B : KID_NONE, "k_rt_vgrad_b", k_rt_vgrad_b<ACC>, rows, MR_VGRAD_NT, 0, st, A.RR,
+                  m->V, m->vadj_ptr, m->vadj, A.gfix, A.gface, A.fflag, A.gverts, A.gcol);
+  if (A.vraw)
+    if (int rc = launch(A.timed ? KID_RT_VGRAD_A : KID_NONE, "k_rt_vgrad_a", k_rt_vgrad_a<ACC>, rows, MR_VGRAD_NT, 0, st,
+                        A.RR, m->V, m->vadj_ptr, m->vadj, A.gfix, A.gface, A.fflag, A.vraw, A.gnu))
+      return rc;
+  return launch(A.timed ? KID_VGRAD_B : KID_NONE, "k_vgrad_b", k_vgrad_b<ACC>, ceil_div(m->V * MR_VL, 256), 256, 0, st,
+                m->V, m->verts, m->faces, m->vadj_ptr, m->vadj, A.gfix, A.gface, A.fflag, A.gnu, A.vraw ? 1 : 0, A.gverts,
+                A.gcol);
 }
 
 // projection: face_verts[n*F+f][c] = ndc(view n, X); distinct meshes (ff = first union face of
