@@ -473,6 +473,43 @@ int32_t mr_sample_points_backward(int64_t V, const int32_t* faces, int64_t F, co
                                   void* stream);
 int32_t mr_face_areas(const float* verts, int64_t V, const int32_t* faces, int64_t F, float* areas, void* stream);
 
+/* Similarity alignment of point clouds (PyTorch3D corresponding_points_alignment and iterative_closest_point;
+ * pytorch3d_icp_registeration.py:154-185). A cloud's transform is 13 floats "rts": R (3x3, row-major), T (3), s,
+ * with y = s (x R) + T for row vectors, evaluated in float32 in that order without FMA.
+ *
+ * mr_points_alignment: rts (N,13) = the transform that takes x (N,P,3) to y (N,P,3) in the weighted least-squares
+ * sense. weights (N,P) >= 0 or NULL (ones); lengths (N) or NULL: points past a cloud's length weigh 0. Means,
+ * covariance (sum w (x - mx)(y - my)^T / max(sum w, eps)) and the 3x3 SVD (one-sided Jacobi, a fixed number of
+ * sweeps) are float64 and summed in a fixed order; R = U E V^T with E = diag(1, 1, det(U V^T)), or the identity with
+ * MR_ICP_ALLOW_REFLECTION; s = tr(E S) / max(sum w |x - mx|^2 / sum w, eps) with MR_ICP_ESTIMATE_SCALE, else 1;
+ * T = my - s mx R. A cloud whose weights sum to 0 gets the identity.
+ *
+ * ICP of x (N,P1,3) onto y (N,P2,3): mr_icp_init sets rts to (R0 (N,3,3), T0 (N,3), s0 (N)) or, all three NULL, the
+ * identity, clears status and prepares the workspace. mr_icp_iterate then enqueues `iterations` iterations without
+ * synchronising: nearest target (squared L2, lowest index on ties, within y_lengths) of every transformed source
+ * point; alignment of the ORIGINAL x to those targets (x_lengths as weights, eps 1e-9) into rts and into slot
+ * status[1] of history (max_iterations,N,13); rmse (N) = sqrt(sum |s x R + T - y_nn|^2 / max(length, 1e-9)) under the
+ * new transform; rel = (previous rmse - rmse) / previous rmse in float32 (1 on the first iteration). status is two
+ * int32 on the device: [0] becomes 1 when rel <= relative_rmse_thr for every cloud (a NaN does not pass), [1] counts
+ * the iterations run. Once status[0] is set or status[1] == max_iterations every further kernel returns at once, so
+ * the caller may enqueue in batches of any size and read status between them: the results do not depend on the
+ * batch size. The same ws, rts, history, rmse and status go to every call of one registration. mr_icp_transform
+ * writes out (N,P,3) = s (x R) + T for every entry of x, with the code the iterations use. */
+enum { MR_ICP_ESTIMATE_SCALE = 1, MR_ICP_ALLOW_REFLECTION = 2, MR_ICP_ALL = 3 };
+size_t mr_icp_workspace(int64_t N, int64_t P1, int64_t P2);
+int32_t mr_icp_init(const float* x, int64_t N, int64_t P1, int64_t P2, const int64_t* x_lengths, const float* R0,
+                    const float* T0, const float* s0, float* rts, int32_t* status, void* ws, size_t ws_bytes,
+                    void* stream);
+int32_t mr_icp_iterate(const float* x, const float* y, int64_t N, int64_t P1, int64_t P2, const int64_t* x_lengths,
+                       const int64_t* y_lengths, int32_t flags, float relative_rmse_thr, int32_t max_iterations,
+                       int32_t iterations, float* rts, float* history, float* rmse, int32_t* status, void* ws,
+                       size_t ws_bytes, void* stream);
+int32_t mr_icp_transform(const float* x, int64_t N, int64_t P, const float* rts, float* out, void* stream);
+size_t mr_points_alignment_workspace(int64_t N, int64_t P);
+int32_t mr_points_alignment(const float* x, const float* y, int64_t N, int64_t P, const int64_t* lengths,
+                            const float* weights, int32_t flags, double eps, float* rts, void* ws, size_t ws_bytes,
+                            void* stream);
+
 /* Work counters left in `workspace` by the last mr_render_forward / mr_rasterize_meshes that used it
  * (same N, total faces, H, W, max_faces_per_bin). Synchronises `stream`; for benchmarks and tools.
  * out[0] = (tile, face) list entries, out[1] = raster work units, out[2] = non-empty 8x8 tiles,

@@ -31,6 +31,7 @@ MR_FRAG_SORTED = 1024  # mr_shade_fragments_*: empty slots follow the filled one
 MR_GRAD_ROWS_CLEARED = 16  # mr_render_backward: first backward over a forward (its face totals are still clear)
 MR_PRIOR_EDGE, MR_PRIOR_LAPLACIAN, MR_PRIOR_NORMAL, MR_PRIOR_ALL = 1, 2, 4, 7  # mr_mesh_priors_*: terms mask
 MR_CHAMFER_POINT_MEAN, MR_CHAMFER_BATCH_MEAN, MR_CHAMFER_BATCH_SUM, MR_CHAMFER_SINGLE = 1, 2, 4, 8  # mr_chamfer_*: flags
+MR_ICP_ESTIMATE_SCALE, MR_ICP_ALLOW_REFLECTION = 1, 2  # mr_icp_iterate / mr_points_alignment: flags
 
 
 class MrView(ctypes.Structure):
@@ -158,6 +159,13 @@ _SIGS = [
     ("mr_chamfer_backward_workspace", _SZ, [_I64, _I64, _I64]),
     ("mr_chamfer_backward", _I32, [_VP, _VP, _I64, _I64, _I64, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ,
                                    _VP]),
+    ("mr_icp_workspace", _SZ, [_I64, _I64, _I64]),
+    ("mr_icp_init", _I32, [_VP, _I64, _I64, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    ("mr_icp_iterate", _I32, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, _I32, ctypes.c_float, _I32, _I32, _VP, _VP, _VP,
+                              _VP, _VP, _SZ, _VP]),
+    ("mr_icp_transform", _I32, [_VP, _I64, _I64, _VP, _VP, _VP]),
+    ("mr_points_alignment_workspace", _SZ, [_I64, _I64]),
+    ("mr_points_alignment", _I32, [_VP, _VP, _I64, _I64, _VP, _VP, _I32, ctypes.c_double, _VP, _VP, _SZ, _VP]),
     ("mr_sample_points_forward", _I32, [_VP, _I64, _VP, _I64, _VP, _VP, _I64, _VP, _VP]),
     ("mr_sample_points_backward_workspace", _SZ, [_I64]),
     ("mr_sample_points_backward", _I32, [_I64, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _SZ, _VP]),

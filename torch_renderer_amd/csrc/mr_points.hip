@@ -21,6 +21,13 @@
 //                   a float remainder row). The rows hold UNSCALED differences: the coefficients are applied after.
 //   k_cham_grad     backward: grad = k (c_own (p - nn(p)) - c_other row(p)), k = 2 or 1, one store per entry.
 //   k_sample_fwd / k_sample_scatter / k_fix_to_float, k_face_areas: see the entry points below.
+//   k_icp_*         iterative_closest_point and corresponding_points_alignment (mr_icp_* / mr_points_alignment). An
+//                   ICP iteration is four launches and no host work: k_icp_nn (k_nn's x -> y direction with the
+//                   cloud's transform applied in registers), k_icp_moments (float64 sums of y_nn and (x - mx) y_nn^T
+//                   per tile), k_icp_solve (every workgroup of a cloud sums the tiles in order and solves the 3x3
+//                   Procrustes problem by a fixed-sweep Jacobi SVD in float64, then sums its tile of the residual
+//                   under the new transform) and k_icp_status (rmse, relative drop, the device status words every
+//                   kernel of a later iteration reads first). No float atomics, every sum in a fixed order.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -55,7 +62,7 @@ bool sizes_ok(int64_t N, int64_t P1, int64_t P2) {
          N * P1 < (1ll << 40) / 3 && N * P2 < (1ll << 40) / 3;
 }
 
-NNGeom nn_geom(int64_t N, int64_t P1, int64_t P2) {
+NNGeom nn_geom(int64_t N, int64_t P1, int64_t P2, int64_t want_groups = MRN_WANT_GROUPS) {
   NNGeom g;
   g.N = N;
   g.P[0] = P1;
@@ -63,7 +70,7 @@ NNGeom nn_geom(int64_t N, int64_t P1, int64_t P2) {
   for (int d = 0; d < 2; ++d) {
     const int64_t Pq = g.P[d], Pt = g.P[1 - d];
     const int64_t qtiles = ceil_div(Pq, MRN_QT);
-    int64_t want = MRN_WANT_GROUPS / (N * qtiles);
+    int64_t want = want_groups / (N * qtiles);
     if (want < 1) want = 1;
     int64_t c = ((Pt + want - 1) / want + 63) / 64 * 64;
     if (c < MRN_MINCHUNK) c = MRN_MINCHUNK;
@@ -416,6 +423,448 @@ bool mesh_sizes_ok(int64_t V, int64_t F, int64_t M) {
   return V >= 0 && F >= 0 && M >= 0 && V < 0x7fffffffll / 3 && F < 0x7fffffffll / 3 && M < (1ll << 31) * MRR_BLOCK / 4;
 }
 
+// ---------------------------------------------------------------------------
+// Similarity alignment and ICP (PyTorch3D corresponding_points_alignment / iterative_closest_point).
+// A cloud's transform is 13 floats, R (3x3 row-major), T (3), s: y = s (x R) + T with row vectors.
+// ---------------------------------------------------------------------------
+#define MRI_RTS 13
+#define MRI_XC 8        // per-cloud constants (double): sum w, mean of x (3), sum w |x - mean|^2, sum w (x - mean) (3)
+#define MRI_MOM 12      // per-workgroup moments (double): sum w y (3), sum w (x - mean) y^T (9, row = x component)
+// k_icp_nn workgroups the target chunk aims for. More than k_nn's: at the registration shape (300 clouds, 2,000
+// sources, 100-400 targets) that is the minimum chunk of 64, whose many short workgroups even out the clouds'
+// different target counts: 9.6 -> 7.9 ms per 97-iteration registration against 1,024 (ICP).
+#ifndef MRI_WANT_GROUPS
+#define MRI_WANT_GROUPS 16384
+#endif
+#define MRI_SWEEPS 10   // Jacobi sweeps of the 3x3 SVD (a converged pair is skipped; the count is fixed)
+
+struct IcpWS {
+  u64* key;       // (N, P1), all-ones between iterations (k_icp_moments resets what it reads)
+  int32_t* idx;   // (N, P1) this iteration's neighbours, -1 for no term
+  double* xc;     // (N, MRI_XC)
+  double* mom;    // (N, nblk, MRI_MOM)
+  double* res;    // (N, nblk)
+  int64_t nblk;
+  size_t key_bytes, bytes;
+};
+IcpWS carve_icp(void* base, int64_t N, int64_t P1) {
+  IcpWS w;
+  Carver c(base);
+  w.key_bytes = sizeof(u64) * (size_t)(N * P1);
+  w.key = c.take<u64>((size_t)(N * P1));
+  w.idx = c.take<int32_t>((size_t)(N * P1));
+  w.xc = c.take<double>((size_t)(N * MRI_XC));
+  w.nblk = ceil_div(P1, MRR_TILE);
+  w.mom = c.take<double>((size_t)(N * w.nblk * MRI_MOM));
+  w.res = c.take<double>((size_t)(N * w.nblk));
+  w.bytes = c.off;
+  return w;
+}
+
+// The one transform code: the NN search, the residual and the final points all call it.
+__device__ __forceinline__ void sim_apply(const float* __restrict__ t, float x0, float x1, float x2, float& o0,
+                                          float& o1, float& o2) {
+  const float s = t[12];
+  o0 = s * ((x0 * t[0] + x1 * t[3]) + x2 * t[6]) + t[9];
+  o1 = s * ((x0 * t[1] + x1 * t[4]) + x2 * t[7]) + t[10];
+  o2 = s * ((x0 * t[2] + x1 * t[5]) + x2 * t[8]) + t[11];
+}
+
+// K sums over a 256-thread workgroup, each in block_sum's tree; sm: 4 * K doubles. Every thread gets the totals.
+template <int K> __device__ __forceinline__ void block_sums(double (&v)[K], double* sm) {
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) sm[(threadIdx.x >> 6) * K + k] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = ((sm[k] + sm[K + k]) + sm[2 * K + k]) + sm[3 * K + k];
+  __syncthreads();
+}
+
+__device__ __forceinline__ float point_weight(const float* __restrict__ weights, int64_t n, int64_t P, int64_t i,
+                                              int64_t len) {
+  if (i >= len) return 0.0f;
+  return weights ? weights[n * P + i] : 1.0f;
+}
+
+// status[0]: the batch has converged; status[1]: iterations run. An iteration's kernels do nothing once either
+// the batch has converged or max_iter iterations have run (the host may enqueue more than are needed).
+__device__ __forceinline__ bool icp_idle(const int32_t* __restrict__ status, int max_iter) {
+  return status && (status[0] != 0 || status[1] >= max_iter || status[1] < 0);
+}
+
+// One workgroup per cloud: its constants xc, and (rts != NULL) its starting transform (R0, T0, s0 or the identity).
+__global__ void __launch_bounds__(MRR_BLOCK) k_icp_xstats(const float* __restrict__ x, int64_t P,
+                                                          const int64_t* __restrict__ xl,
+                                                          const float* __restrict__ weights, double eps,
+                                                          double* __restrict__ xc, const float* __restrict__ R0,
+                                                          const float* __restrict__ T0, const float* __restrict__ s0,
+                                                          float* __restrict__ rts) {
+  __shared__ double sm[4 * 4];
+  const int64_t n = blockIdx.x;
+  const int64_t len = cloud_len(xl, n, P);
+  const float* __restrict__ q = x + 3 * n * P;
+  double a[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int64_t i = threadIdx.x; i < len; i += MRR_BLOCK) {
+    const double w = (double)point_weight(weights, n, P, i, len);
+    a[0] += w;
+    a[1] += w * (double)q[3 * i];
+    a[2] += w * (double)q[3 * i + 1];
+    a[3] += w * (double)q[3 * i + 2];
+  }
+  block_sums<4>(a, sm);
+  const double wc = a[0] > eps ? a[0] : eps;
+  const double m0 = a[1] / wc, m1 = a[2] / wc, m2 = a[3] / wc;
+  double b[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int64_t i = threadIdx.x; i < len; i += MRR_BLOCK) {
+    const double w = (double)point_weight(weights, n, P, i, len);
+    const double d0 = (double)q[3 * i] - m0, d1 = (double)q[3 * i + 1] - m1, d2 = (double)q[3 * i + 2] - m2;
+    b[0] += w * ((d0 * d0 + d1 * d1) + d2 * d2);
+    b[1] += w * d0;
+    b[2] += w * d1;
+    b[3] += w * d2;
+  }
+  block_sums<4>(b, sm);
+  if (threadIdx.x == 0) {
+    double* o = xc + n * MRI_XC;
+    o[0] = a[0];
+    o[1] = m0;
+    o[2] = m1;
+    o[3] = m2;
+    o[4] = b[0];
+    o[5] = b[1];
+    o[6] = b[2];
+    o[7] = b[3];
+  }
+  if (rts && threadIdx.x < MRI_RTS) {
+    const int k = threadIdx.x;
+    float v;
+    if (k < 9) v = R0 ? R0[n * 9 + k] : ((k == 0 || k == 4 || k == 8) ? 1.0f : 0.0f);
+    else if (k < 12) v = T0 ? T0[n * 3 + (k - 9)] : 0.0f;
+    else v = s0 ? s0[n] : 1.0f;
+    rts[n * MRI_RTS + k] = v;
+  }
+}
+
+// k_nn's direction x -> y with the cloud's current transform applied to the queries in registers.
+__global__ void __launch_bounds__(MRN_BLOCK) k_icp_nn(const float* __restrict__ x, const float* __restrict__ y, NNGeom g,
+                                                      const int64_t* __restrict__ xl, const int64_t* __restrict__ yl,
+                                                      const float* __restrict__ rts,
+                                                      const int32_t* __restrict__ status, int max_iter,
+                                                      u64* __restrict__ key_x) {
+  __shared__ float4 sm[MRN_MAXCHUNK];
+  if (icp_idle(status, max_iter)) return;
+  if ((int64_t)blockIdx.x >= g.groups[0]) return;
+  const int64_t n = blockIdx.y;
+  const int64_t Pq = g.P[0], Pt = g.P[1];
+  const float* __restrict__ q = x + 3 * n * Pq;
+  const float* __restrict__ t = y + 3 * n * Pt;
+  const int64_t lq = cloud_len(xl, n, Pq), lt = cloud_len(yl, n, Pt);
+  const int64_t q0 = ((int64_t)blockIdx.x / g.nchunk[0]) * MRN_QT;
+  const int64_t t0 = ((int64_t)blockIdx.x % g.nchunk[0]) * g.chunk[0];
+  if (q0 >= lq || t0 >= lt) return;  // uniform over the workgroup
+  const int cnt = (int)((lt - t0 < g.chunk[0]) ? lt - t0 : g.chunk[0]);
+  for (int j = threadIdx.x; j < cnt; j += MRN_BLOCK) {
+    const float* p = t + 3 * (t0 + j);
+    sm[j] = make_float4(p[0], p[1], p[2], 0.0f);
+  }
+  __syncthreads();
+
+  const float* __restrict__ tr = rts + n * MRI_RTS;
+  float qx[MRN_Q], qy[MRN_Q], qz[MRN_Q], best[MRN_Q];
+  int bi[MRN_Q];
+#pragma unroll
+  for (int k = 0; k < MRN_Q; ++k) {
+    const int64_t i = q0 + k * MRN_BLOCK + threadIdx.x;
+    const bool ok = i < lq;
+    sim_apply(tr, ok ? q[3 * i] : 0.0f, ok ? q[3 * i + 1] : 0.0f, ok ? q[3 * i + 2] : 0.0f, qx[k], qy[k], qz[k]);
+    best[k] = __builtin_inff();
+    bi[k] = 0;
+  }
+#pragma unroll 4
+  for (int j = 0; j < cnt; ++j) {
+    const float4 p = sm[j];
+#pragma unroll
+    for (int k = 0; k < MRN_Q; ++k) {
+      const float dd = dist3<2>(qx[k], qy[k], qz[k], p);
+      if (dd < best[k]) {  // strict: the lowest index wins a tie inside the chunk
+        best[k] = dd;
+        bi[k] = j;
+      }
+    }
+  }
+  u64* __restrict__ key = key_x + n * Pq;
+#pragma unroll
+  for (int k = 0; k < MRN_Q; ++k) {
+    const int64_t i = q0 + k * MRN_BLOCK + threadIdx.x;
+    if (i < lq) atomicMin(&key[i], ((u64)__float_as_uint(best[k]) << 32) | (u64)(uint32_t)(t0 + bi[k]));
+  }
+}
+
+// grid (nblk, N): the moments of a tile of source points against their correspondences. key != NULL: the
+// correspondence of point i is the index in key[i] (left in idx[i]; the key is set back to all-ones for the next
+// search); key == NULL: point i of y.
+__global__ void __launch_bounds__(MRR_BLOCK) k_icp_moments(const float* __restrict__ x, const float* __restrict__ y,
+                                                           int64_t P1, int64_t P2, const int64_t* __restrict__ xl,
+                                                           const int64_t* __restrict__ yl,
+                                                           const float* __restrict__ weights,
+                                                           const double* __restrict__ xc,
+                                                           const int32_t* __restrict__ status, int max_iter,
+                                                           u64* __restrict__ key, int32_t* __restrict__ idx,
+                                                           double* __restrict__ mom, int64_t nblk) {
+  __shared__ double sm[4 * MRI_MOM];
+  if (icp_idle(status, max_iter)) return;
+  const int64_t n = blockIdx.y;
+  const int64_t lx = cloud_len(xl, n, P1), lt = cloud_len(yl, n, P2);
+  const double m0 = xc[n * MRI_XC + 1], m1 = xc[n * MRI_XC + 2], m2 = xc[n * MRI_XC + 3];
+  double a[MRI_MOM];
+#pragma unroll
+  for (int k = 0; k < MRI_MOM; ++k) a[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k < MRR_PER; ++k) {
+    const int64_t i = (int64_t)blockIdx.x * MRR_TILE + k * MRR_BLOCK + threadIdx.x;
+    if (i >= P1) continue;
+    int64_t j = -1;
+    if (i < lx) {
+      if (key) {
+        const u64 kk = key[n * P1 + i];
+        key[n * P1 + i] = ~0ull;
+        j = (int64_t)(uint32_t)kk;
+      } else {
+        j = i;
+      }
+      if (j >= lt) j = -1;  // no target (an empty target cloud leaves the key untouched)
+    }
+    if (idx) idx[n * P1 + i] = (int32_t)j;
+    if (j < 0) continue;
+    const double w = (double)point_weight(weights, n, P1, i, lx);
+    const float* __restrict__ q = x + 3 * (n * P1 + i);
+    const float* __restrict__ t = y + 3 * (n * P2 + j);
+    const double y0 = (double)t[0], y1 = (double)t[1], y2 = (double)t[2];
+    const double d0 = w * ((double)q[0] - m0), d1 = w * ((double)q[1] - m1), d2 = w * ((double)q[2] - m2);
+    a[0] += w * y0;
+    a[1] += w * y1;
+    a[2] += w * y2;
+    a[3] += d0 * y0;
+    a[4] += d0 * y1;
+    a[5] += d0 * y2;
+    a[6] += d1 * y0;
+    a[7] += d1 * y1;
+    a[8] += d1 * y2;
+    a[9] += d2 * y0;
+    a[10] += d2 * y1;
+    a[11] += d2 * y2;
+  }
+  block_sums<MRI_MOM>(a, sm);
+  if (threadIdx.x < MRI_MOM) {
+    double v = 0.0;
+#pragma unroll
+    for (int k = 0; k < MRI_MOM; ++k) v = threadIdx.x == k ? a[k] : v;
+    mom[(n * nblk + blockIdx.x) * MRI_MOM + threadIdx.x] = v;
+  }
+}
+
+__host__ __device__ __forceinline__ double det3(const double (&m)[3][3]) {
+  return m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
+         m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+}
+
+// The similarity transform of one cloud from its constants and its moment partials (summed in order), in float64:
+// cov = sum w (x - mx)(y - my)^T / wc = U S V^T by a one-sided Jacobi (the columns of W = cov V are rotated until
+// orthogonal: S = their norms, U = them normalised), R = U E V^T with E = diag(1, 1, det(U V^T)) unless
+// reflections are allowed, s = tr(E S) / max(sum w |x - mx|^2 / wc, eps) or 1, T = my - s mx R. A cloud without
+// weight gives the identity. (Also a host function, so that a CPU program can check the solve against LAPACK.)
+__host__ __device__ void solve_cloud(const double* __restrict__ c, const double* __restrict__ mom, int64_t nblk, int flags,
+                            double eps, float* out) {
+  double m[MRI_MOM];
+  for (int k = 0; k < MRI_MOM; ++k) m[k] = 0.0;
+  for (int64_t b = 0; b < nblk; ++b)
+    for (int k = 0; k < MRI_MOM; ++k) m[k] += mom[b * MRI_MOM + k];
+  if (!(c[0] > 0.0)) {
+    for (int k = 0; k < MRI_RTS; ++k) out[k] = (k == 0 || k == 4 || k == 8 || k == 12) ? 1.0f : 0.0f;
+    return;
+  }
+  const double wc = c[0] > eps ? c[0] : eps;
+  const double my[3] = {m[0] / wc, m[1] / wc, m[2] / wc};
+  double W[3][3], V[3][3];
+  double big = 0.0;
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) {
+      W[a][b] = (m[3 + 3 * a + b] - c[5 + a] * my[b]) / wc;
+      V[a][b] = a == b ? 1.0 : 0.0;
+      big = fabs(W[a][b]) > big ? fabs(W[a][b]) : big;
+    }
+  const double unit = (big > 0.0 && big < 1e300) ? big : 1.0;  // the rotations see entries of magnitude <= 1
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) W[a][b] /= unit;
+  for (int sweep = 0; sweep < MRI_SWEEPS; ++sweep)
+    for (int pr = 0; pr < 3; ++pr) {
+      const int p = pr == 2 ? 1 : 0, q = pr == 0 ? 1 : 2;
+      const double al = (W[0][p] * W[0][p] + W[1][p] * W[1][p]) + W[2][p] * W[2][p];
+      const double be = (W[0][q] * W[0][q] + W[1][q] * W[1][q]) + W[2][q] * W[2][q];
+      const double ga = (W[0][p] * W[0][q] + W[1][p] * W[1][q]) + W[2][p] * W[2][q];
+      if (!(ga * ga > 1e-36 * (al * be))) continue;  // orthogonal already (or a zero column)
+      const double ze = (be - al) / (2.0 * ga);
+      const double tt = (ze >= 0.0 ? 1.0 : -1.0) / (fabs(ze) + sqrt(1.0 + ze * ze));
+      const double cs = 1.0 / sqrt(1.0 + tt * tt), sn = cs * tt;
+      for (int a = 0; a < 3; ++a) {
+        const double wp = W[a][p], wq = W[a][q], vp = V[a][p], vq = V[a][q];
+        W[a][p] = cs * wp - sn * wq;
+        W[a][q] = sn * wp + cs * wq;
+        V[a][p] = cs * vp - sn * vq;
+        V[a][q] = sn * vp + cs * vq;
+      }
+    }
+  double sg[3];
+  for (int j = 0; j < 3; ++j) sg[j] = sqrt((W[0][j] * W[0][j] + W[1][j] * W[1][j]) + W[2][j] * W[2][j]);
+  for (int pr = 0; pr < 3; ++pr) {  // descending singular values: (0,1), (1,2), (0,1)
+    const int p = pr == 1 ? 1 : 0, q = p + 1;
+    if (sg[p] < sg[q]) {
+      const double ts = sg[p];
+      sg[p] = sg[q];
+      sg[q] = ts;
+      for (int a = 0; a < 3; ++a) {
+        const double tw = W[a][p], tv = V[a][p];
+        W[a][p] = W[a][q];
+        W[a][q] = tw;
+        V[a][p] = V[a][q];
+        V[a][q] = tv;
+      }
+    }
+  }
+  double U[3][3];
+  const double tiny = 1e-13 * sg[0];
+  if (sg[0] > 0.0) {
+    for (int a = 0; a < 3; ++a) U[a][0] = W[a][0] / sg[0];
+  } else {
+    U[0][0] = 1.0;
+    U[1][0] = U[2][0] = 0.0;
+  }
+  if (sg[1] > tiny) {
+    for (int a = 0; a < 3; ++a) U[a][1] = W[a][1] / sg[1];
+  } else {  // any unit vector orthogonal to the first: from the axis the first is least along
+    int k = 0;
+    if (fabs(U[1][0]) < fabs(U[k][0])) k = 1;
+    if (fabs(U[2][0]) < fabs(U[k][0])) k = 2;
+    double v[3], nn = 0.0;
+    for (int a = 0; a < 3; ++a) {
+      v[a] = (a == k ? 1.0 : 0.0) - U[k][0] * U[a][0];
+      nn += v[a] * v[a];
+    }
+    nn = sqrt(nn);
+    for (int a = 0; a < 3; ++a) U[a][1] = v[a] / nn;
+  }
+  if (sg[2] > tiny) {
+    for (int a = 0; a < 3; ++a) U[a][2] = W[a][2] / sg[2];
+  } else {
+    U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
+    U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
+    U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
+  }
+  const double e2 = (flags & MR_ICP_ALLOW_REFLECTION) ? 1.0 : (det3(U) * det3(V) < 0.0 ? -1.0 : 1.0);
+  double R[3][3];
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) R[a][b] = (U[a][0] * V[b][0] + U[a][1] * V[b][1]) + e2 * (U[a][2] * V[b][2]);
+  double s = 1.0;
+  if (flags & MR_ICP_ESTIMATE_SCALE) {
+    const double xcov = c[4] / wc;
+    s = (((sg[0] + sg[1]) + e2 * sg[2]) * unit) / (xcov > eps ? xcov : eps);
+  }
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) out[3 * a + b] = (float)R[a][b];
+  for (int b = 0; b < 3; ++b) out[9 + b] = (float)(my[b] - s * ((c[1] * R[0][b] + c[2] * R[1][b]) + c[3] * R[2][b]));
+  out[12] = (float)s;
+}
+
+// grid (nblk or 1, N). Thread 0 of every workgroup solves its cloud (the same inputs and code: the same bits in every
+// workgroup of the cloud); workgroup 0 stores the transform in rts and, with hist, in slot status[1] of the history.
+// res != NULL: the workgroup's tile of the residual sum w |s x R + T - y_nn|^2 with that transform.
+__global__ void __launch_bounds__(MRR_BLOCK) k_icp_solve(const float* __restrict__ x, const float* __restrict__ y,
+                                                         int64_t N, int64_t P1, int64_t P2,
+                                                         const int64_t* __restrict__ xl,
+                                                         const float* __restrict__ weights,
+                                                         const double* __restrict__ xc, const double* __restrict__ mom,
+                                                         int64_t nblk, const int32_t* __restrict__ idx, int flags,
+                                                         double eps, const int32_t* __restrict__ status, int max_iter,
+                                                         float* __restrict__ rts, float* __restrict__ hist,
+                                                         double* __restrict__ res) {
+  __shared__ double sm[4];
+  __shared__ float tr[MRI_RTS];
+  if (icp_idle(status, max_iter)) return;
+  const int64_t n = blockIdx.y;
+  if (threadIdx.x == 0) solve_cloud(xc + n * MRI_XC, mom + n * nblk * MRI_MOM, nblk, flags, eps, tr);
+  __syncthreads();
+  if (blockIdx.x == 0 && threadIdx.x < MRI_RTS) {
+    rts[n * MRI_RTS + threadIdx.x] = tr[threadIdx.x];
+    if (hist) hist[((int64_t)status[1] * N + n) * MRI_RTS + threadIdx.x] = tr[threadIdx.x];
+  }
+  if (!res) return;
+  const int64_t lx = cloud_len(xl, n, P1);
+  double acc = 0.0;
+#pragma unroll
+  for (int k = 0; k < MRR_PER; ++k) {
+    const int64_t i = (int64_t)blockIdx.x * MRR_TILE + k * MRR_BLOCK + threadIdx.x;
+    if (i >= lx) continue;
+    const int32_t j = idx[n * P1 + i];
+    if (j < 0 || j >= P2) continue;
+    const float* __restrict__ q = x + 3 * (n * P1 + i);
+    const float* __restrict__ t = y + 3 * (n * P2 + j);
+    float o0, o1, o2;
+    sim_apply(tr, q[0], q[1], q[2], o0, o1, o2);
+    const double d0 = (double)o0 - (double)t[0], d1 = (double)o1 - (double)t[1], d2 = (double)o2 - (double)t[2];
+    acc += (double)point_weight(weights, n, P1, i, lx) * ((d0 * d0 + d1 * d1) + d2 * d2);
+  }
+  acc = block_sum(acc, sm);
+  if (threadIdx.x == 0) res[n * nblk + blockIdx.x] = acc;
+}
+
+// One workgroup: per cloud rmse = sqrt(residual / max(sum w, eps)) and its relative drop against the previous
+// iteration's (float32; 1 on the first iteration, a NaN does not count as converged); then the status words.
+// rmse holds the previous iteration's values on entry.
+__global__ void __launch_bounds__(MRR_BLOCK) k_icp_status(const double* __restrict__ res, int64_t nblk, int64_t N,
+                                                          const double* __restrict__ xc, double eps, float thr,
+                                                          int max_iter, float* __restrict__ rmse,
+                                                          int32_t* __restrict__ status) {
+  __shared__ double sm[4];
+  if (icp_idle(status, max_iter)) return;  // uniform
+  const int it = status[1];
+  double open = 0.0;
+  for (int64_t n = threadIdx.x; n < N; n += MRR_BLOCK) {
+    double s = 0.0;
+    for (int64_t b = 0; b < nblk; ++b) s += res[n * nblk + b];
+    const double wc = xc[n * MRI_XC] > eps ? xc[n * MRI_XC] : eps;
+    const float r = (float)sqrt(s / wc);
+    const float prev = rmse[n];
+    const float rel = it == 0 ? 1.0f : (prev - r) / prev;
+    if (!(rel <= thr)) open += 1.0;
+    rmse[n] = r;
+  }
+  open = block_sum(open, sm);  // also orders every thread's read of status[1] before its update
+  if (threadIdx.x == 0) {
+    status[1] = it + 1;
+    if (open == 0.0) status[0] = 1;
+  }
+}
+
+// out[n, i] = s (x[n, i] R) + T for every entry of the padded tensor.
+__global__ void __launch_bounds__(MRR_BLOCK) k_icp_apply(const float* __restrict__ x, int64_t P,
+                                                         const float* __restrict__ rts, float* __restrict__ out) {
+  const int64_t n = blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * MRR_BLOCK + threadIdx.x;
+  if (i >= P) return;
+  const float* __restrict__ q = x + 3 * (n * P + i);
+  float o0, o1, o2;
+  sim_apply(rts + n * MRI_RTS, q[0], q[1], q[2], o0, o1, o2);
+  float* __restrict__ o = out + 3 * (n * P + i);
+  o[0] = o0;
+  o[1] = o1;
+  o[2] = o2;
+}
+
 }  // namespace
 
 extern "C" {
@@ -531,6 +980,109 @@ int32_t mr_face_areas(const float* verts, int64_t V, const int32_t* faces, int64
   if (!verts || !faces || !areas) return set_err(MR_EINVAL, "face areas: NULL pointer");
   return launch(KID_NONE, "k_face_areas", k_face_areas, ceil_div(F, MRR_BLOCK), MRR_BLOCK, 0, (hipStream_t)stream, verts, V,
                 faces, F, areas);
+}
+
+size_t mr_icp_workspace(int64_t N, int64_t P1, int64_t P2) {
+  if (!sizes_ok(N, P1, P2)) return 0;
+  return carve_icp(nullptr, N, P1).bytes;
+}
+
+static int check_icp(const char* who, const float* x, int64_t N, int64_t P1, int64_t P2) {
+  if (N < 1 || P1 < 1 || P2 < 1) return set_err(MR_EINVAL, "%s: N, P1 and P2 must be >= 1", who);
+  if (!sizes_ok(N, P1, P2))
+    return set_err(MR_EUNSUPPORTED, "%s: more than 65535 clouds or clouds too large for 32-bit point ids", who);
+  if (!x) return set_err(MR_EINVAL, "%s: x is NULL", who);
+  return MR_OK;
+}
+
+int32_t mr_icp_init(const float* x, int64_t N, int64_t P1, int64_t P2, const int64_t* x_lengths, const float* R0,
+                    const float* T0, const float* s0, float* rts, int32_t* status, void* ws, size_t ws_bytes,
+                    void* stream) {
+  if (int rc = check_icp("icp init", x, N, P1, P2)) return rc;
+  if (!rts || !status || !ws) return set_err(MR_EINVAL, "icp init: rts / status / workspace is NULL");
+  if ((R0 || T0 || s0) && !(R0 && T0 && s0)) return set_err(MR_EINVAL, "icp init: R0, T0 and s0 go together");
+  const IcpWS w = carve_icp(ws, N, P1);
+  if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "icp workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  if (int rc = memset_async(w.key, 0xff, w.key_bytes, st)) return rc;
+  if (int rc = memset_async(status, 0, 2 * sizeof(int32_t), st)) return rc;
+  return launch(KID_NONE, "k_icp_xstats", k_icp_xstats, (unsigned)N, MRR_BLOCK, 0, st, x, P1, x_lengths, (const float*)nullptr,
+                1e-9, w.xc, R0, T0, s0, rts);
+}
+
+int32_t mr_icp_iterate(const float* x, const float* y, int64_t N, int64_t P1, int64_t P2, const int64_t* x_lengths,
+                       const int64_t* y_lengths, int32_t flags, float relative_rmse_thr, int32_t max_iterations,
+                       int32_t iterations, float* rts, float* history, float* rmse, int32_t* status, void* ws,
+                       size_t ws_bytes, void* stream) {
+  if (int rc = check_icp("icp", x, N, P1, P2)) return rc;
+  if (flags & ~MR_ICP_ALL) return set_err(MR_EINVAL, "icp: unknown bits in flags");
+  if (max_iterations < 1 || iterations < 0 || (int64_t)max_iterations * N > (1ll << 40) / MRI_RTS)
+    return set_err(MR_EINVAL, "icp: max_iterations must be >= 1 (and the history addressable), iterations >= 0");
+  if (!y || !rts || !history || !rmse || !status || !ws) return set_err(MR_EINVAL, "icp: NULL pointer");
+  const IcpWS w = carve_icp(ws, N, P1);
+  if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "icp workspace too small");
+  const NNGeom g = nn_geom(N, P1, P2, MRI_WANT_GROUPS);
+  if (g.groups[0] > 0x7fffffffll) return set_err(MR_EUNSUPPORTED, "icp: P1 * P2 is too large for one launch");
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 gn((unsigned)g.groups[0], (unsigned)N), gt((unsigned)w.nblk, (unsigned)N);
+  for (int it = 0; it < iterations; ++it) {
+    if (int rc = launch(KID_NONE, "k_icp_nn", k_icp_nn, gn, MRN_BLOCK, 0, st, x, y, g, x_lengths, y_lengths, (const float*)rts,
+                        (const int32_t*)status, max_iterations, w.key))
+      return rc;
+    if (int rc = launch(KID_NONE, "k_icp_moments", k_icp_moments, gt, MRR_BLOCK, 0, st, x, y, P1, P2, x_lengths, y_lengths,
+                        (const float*)nullptr, (const double*)w.xc, (const int32_t*)status, max_iterations, w.key, w.idx,
+                        w.mom, w.nblk))
+      return rc;
+    if (int rc = launch(KID_NONE, "k_icp_solve", k_icp_solve, gt, MRR_BLOCK, 0, st, x, y, N, P1, P2, x_lengths,
+                        (const float*)nullptr, (const double*)w.xc, (const double*)w.mom, w.nblk, (const int32_t*)w.idx,
+                        flags, 1e-9, (const int32_t*)status, max_iterations, rts, history, w.res))
+      return rc;
+    if (int rc = launch(KID_NONE, "k_icp_status", k_icp_status, 1, MRR_BLOCK, 0, st, (const double*)w.res, w.nblk, N,
+                        (const double*)w.xc, 1e-9, relative_rmse_thr, max_iterations, rmse, status))
+      return rc;
+  }
+  return MR_OK;
+}
+
+int32_t mr_icp_transform(const float* x, int64_t N, int64_t P, const float* rts, float* out, void* stream) {
+  if (int rc = check_icp("icp transform", x, N, P, 1)) return rc;
+  if (!rts || !out) return set_err(MR_EINVAL, "icp transform: rts / out is NULL");
+  return launch(KID_NONE, "k_icp_apply", k_icp_apply, dim3((unsigned)ceil_div(P, MRR_BLOCK), (unsigned)N), MRR_BLOCK, 0,
+                (hipStream_t)stream, x, P, rts, out);
+}
+
+size_t mr_points_alignment_workspace(int64_t N, int64_t P) {
+  if (!sizes_ok(N, P, P)) return 0;
+  Carver c(nullptr);
+  c.take<double>((size_t)(N * MRI_XC));
+  c.take<double>((size_t)(N * ceil_div(P, MRR_TILE) * MRI_MOM));
+  return c.off;
+}
+
+int32_t mr_points_alignment(const float* x, const float* y, int64_t N, int64_t P, const int64_t* lengths,
+                            const float* weights, int32_t flags, double eps, float* rts, void* ws, size_t ws_bytes,
+                            void* stream) {
+  if (int rc = check_icp("points alignment", x, N, P, P)) return rc;
+  if (flags & ~MR_ICP_ALL) return set_err(MR_EINVAL, "points alignment: unknown bits in flags");
+  if (!(eps >= 0.0)) return set_err(MR_EINVAL, "points alignment: eps must be >= 0");
+  if (!y || !rts || !ws) return set_err(MR_EINVAL, "points alignment: NULL pointer");
+  if (ws_bytes < mr_points_alignment_workspace(N, P)) return set_err(MR_EWORKSPACE, "points alignment workspace too small");
+  Carver c(ws);
+  double* xc = c.take<double>((size_t)(N * MRI_XC));
+  const int64_t nblk = ceil_div(P, MRR_TILE);
+  double* mom = c.take<double>((size_t)(N * nblk * MRI_MOM));
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 gt((unsigned)nblk, (unsigned)N);
+  const float* nof = nullptr;
+  const int32_t* noi = nullptr;
+  if (int rc = launch(KID_NONE, "k_icp_xstats", k_icp_xstats, (unsigned)N, MRR_BLOCK, 0, st, x, P, lengths, weights, eps, xc, nof,
+                      nof, nof, (float*)nullptr))
+    return rc;
+  if (int rc = launch(KID_NONE, "k_icp_moments", k_icp_moments, gt, MRR_BLOCK, 0, st, x, y, P, P, lengths, lengths, weights,
+                      (const double*)xc, noi, 0, (u64*)nullptr, (int32_t*)nullptr, mom, nblk))
+    return rc;
+  return launch(KID_NONE, "k_icp_solve", k_icp_solve, dim3(1, (unsigned)N), MRR_BLOCK, 0, st, x, y, N, P, P, lengths, weights,
+                (const double*)xc, (const double*)mom, nblk, noi, flags, eps, noi, 0, rts, (float*)nullptr, (double*)nullptr);
 }
 
 }  // extern "C"

@@ -314,6 +314,74 @@ class ChamferDistance(torch.autograd.Function):
         return gx.to(xdt), gy.to(ydt), None, None, None, None, None
 
 
+# Iterations enqueued between two reads of the device status: a read costs ~14 us, an iteration enqueued after
+# convergence ~18 us (tools/icp_bench.py, DESIGN.md §3, ICP)
+ICP_STATUS_BATCH = 8
+
+
+def points_alignment(x, y, lengths=None, weights=None, flags=0, eps=1e-9):
+    """rts (N,13) float32 = (R row-major, T, s) per cloud of the similarity transform taking x (N,P,3) to y (N,P,3):
+    three launches, nothing read back (mr_points_alignment). weights (N,P) and lengths (N) may be None."""
+    xf, yf, xl, _, N, P, _ = _cloud_args(x, y, lengths, None, 2)
+    _require_cuda(weights)
+    w = None if weights is None else weights.detach().float().contiguous()
+    L = _lib.load()
+    dev = xf.device
+    rts = torch.empty((N, 13), device=dev)
+    wsb = _ws_size(L.mr_points_alignment_workspace, N, P)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    check(L.mr_points_alignment(ptr(xf), ptr(yf), N, P, ptr(xl), ptr(w), int(flags), float(eps), ptr(rts), ptr(ws),
+                                wsb, _lib.stream_handle(dev)))
+    return rts
+
+
+def similarity_transform(x, rts):
+    """s (x R) + T for every entry of x (N,P,3) with the library's transform code (mr_icp_transform)."""
+    _require_cuda(x, rts)
+    xf = x.detach().float().contiguous()
+    out = torch.empty_like(xf)
+    check(_lib.load().mr_icp_transform(ptr(xf), xf.shape[0], xf.shape[1], ptr(rts), ptr(out),
+                                       _lib.stream_handle(xf.device)))
+    return out
+
+
+def icp(x, y, x_lengths=None, y_lengths=None, init=None, max_iterations=100, relative_rmse_thr=1e-6, flags=0,
+        status_batch=None):
+    """The ICP loop on the device (mr_icp_*): (converged, iterations run, rmse (N) or None, Xt (N,P1,3), rts (N,13),
+    history (iterations,N,13)). ``init`` = (R (N,3,3), T (N,3), s (N)) or None. The host enqueues ``status_batch``
+    iterations at a time (default ICP_STATUS_BATCH) and reads two status words between the batches; the results do
+    not depend on that size."""
+    xf, yf, xl, yl, N, P1, P2 = _cloud_args(x, y, x_lengths, y_lengths, 2)
+    L = _lib.load()
+    dev = xf.device
+    st = _lib.stream_handle(dev)
+    R0 = T0 = s0 = None
+    if init is not None:
+        _require_cuda(*init)
+        R0, T0, s0 = (t.detach().float().contiguous() for t in init)
+    max_iterations = int(max_iterations)
+    rts = torch.empty((N, 13), device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    wsb = _ws_size(L.mr_icp_workspace, N, P1, P2)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    check(L.mr_icp_init(ptr(xf), N, P1, P2, ptr(xl), ptr(R0), ptr(T0), ptr(s0), ptr(rts), ptr(status), ptr(ws), wsb, st))
+    done, iters, rmse = 0, 0, None
+    hist = torch.empty((max(max_iterations, 0), N, 13), device=dev)
+    if max_iterations > 0:
+        rmse = torch.empty(N, device=dev)
+        batch = max(int(status_batch or ICP_STATUS_BATCH), 1)
+        left = max_iterations
+        while left > 0 and not done:
+            k = min(batch, left)
+            check(L.mr_icp_iterate(ptr(xf), ptr(yf), N, P1, P2, ptr(xl), ptr(yl), int(flags), float(relative_rmse_thr),
+                                   max_iterations, k, ptr(rts), ptr(hist), ptr(rmse), ptr(status), ptr(ws), wsb, st))
+            left -= k
+            done, iters = status.tolist()  # the one synchronisation of a batch
+    xt = torch.empty_like(xf)
+    check(L.mr_icp_transform(ptr(xf), N, P1, ptr(rts), ptr(xt), st))
+    return bool(done), iters, rmse, xt, rts, hist[:iters]
+
+
 def _mesh_args(verts, faces):
     _require_cuda(verts, faces)
     if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:

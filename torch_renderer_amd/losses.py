@@ -38,6 +38,7 @@ import torch
 
 from . import _lib
 from .kernels import ChamferDistance, MeshShapePriors, _require_cuda, mesh_prior_topology
+from .structures import Pointclouds
 
 
 def _rgba_base(t: torch.Tensor, channels):
@@ -121,9 +122,24 @@ def mesh_normal_consistency(meshes):
     return _mesh_priors(meshes, 0.0, _lib.MR_PRIOR_NORMAL)[2]
 
 
+def _cloud_input(points, lengths, name):
+    """(padded tensor, lengths) of a chamfer_distance input: a Pointclouds brings its own lengths (None when no cloud
+    is padded, which is decided on the host)."""
+    if isinstance(points, Pointclouds):
+        if lengths is not None:
+            raise ValueError(f"{name} must be None for a Pointclouds input: the lengths are the clouds'")
+        padded = points.points_padded()
+        full = all(c == padded.shape[1] for c in points.counts())
+        return padded, None if full else points.num_points_per_cloud()
+    if not torch.is_tensor(points):
+        raise NotImplementedError("chamfer_distance: the inputs are (N, P, 3) tensors or Pointclouds")
+    return points, lengths
+
+
 def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_normals=None, weights=None,
                      batch_reduction="mean", point_reduction="mean", norm: int = 2, single_directional: bool = False):
-    """pytorch3d.loss.chamfer_distance for (N,P,3) tensors: per cloud the sum (``point_reduction="sum"``) or the mean
+    """pytorch3d.loss.chamfer_distance for (N,P,3) tensors or Pointclouds (whose lengths are then the clouds' own;
+    explicit ``x_lengths`` / ``y_lengths`` beside a Pointclouds raise ValueError): per cloud the sum (``point_reduction="sum"``) or the mean
     over max(length, 1) points (``"mean"``) of every point's distance to its nearest point of the other cloud
     (squared L2 for ``norm=2``, L1 for ``norm=1``), x -> y plus y -> x (x -> y alone with ``single_directional``),
     times ``weights`` (N,); then summed over the batch (``batch_reduction="sum"``), divided by sum(weights) or N
@@ -140,8 +156,8 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_nor
         raise ValueError('point_reduction must be one of ["mean", "sum"] or None')
     if norm not in (1, 2):
         raise ValueError("Support for 1 or 2 norm.")
-    if not torch.is_tensor(x) or not torch.is_tensor(y):
-        raise NotImplementedError("chamfer_distance: only (N, P, 3) tensors are built (no Pointclouds)")
+    x, x_lengths = _cloud_input(x, x_lengths, "x_lengths")
+    y, y_lengths = _cloud_input(y, y_lengths, "y_lengths")
     if x.dim() != 3 or y.dim() != 3:
         raise ValueError("Expected points to be of shape (N, P, D)")
     if x.shape[2] != 3 or y.shape[2] != 3:

@@ -5,16 +5,130 @@ The random draws are torch calls on the meshes' device — ``torch.multinomial``
 (with replacement) and ``torch.rand(2, N, S)`` — so ``torch.manual_seed`` reproduces a call. The face areas
 (kernels.face_areas) and the construction of the points with its backward (kernels.SamplePoints) are native
 (csrc/mr_points.hip).
+
+``iterative_closest_point`` and ``corresponding_points_alignment`` (pytorch3d_icp_registeration.py:154-185,
+pytorch3d_icp_evaluation.py) take (N, P, 3) tensors or ``Pointclouds``; the ICP loop, its nearest-neighbour search,
+the Procrustes solve and the convergence test run on the device (kernels.icp / kernels.points_alignment, the
+k_icp_* kernels of csrc/mr_points.hip). Neither is differentiable.
 """
 from __future__ import annotations
 
+import warnings
 import weakref
+from typing import NamedTuple, Optional
 
 import torch
 
+from . import _lib, kernels
 from .kernels import SamplePoints, _require_cuda, face_areas
+from .structures import Pointclouds
 
 _FACES_CACHE: dict = {}
+
+
+class SimilarityTransform(NamedTuple):
+    R: torch.Tensor
+    T: torch.Tensor
+    s: torch.Tensor
+
+
+class ICPSolution(NamedTuple):
+    converged: bool
+    rmse: Optional[torch.Tensor]
+    Xt: object
+    RTs: SimilarityTransform
+    t_history: list
+
+
+def _clouds_and_lengths(pc, who):
+    """(padded (N,P,D) tensor, host-side counts or None, lengths tensor or None) of a tensor or a Pointclouds."""
+    if isinstance(pc, Pointclouds):
+        counts = pc.counts()
+        padded = pc.points_padded()
+        if all(c == padded.shape[1] for c in counts):
+            return padded, counts, None
+        return padded, counts, pc.num_points_per_cloud()
+    if not torch.is_tensor(pc):
+        raise ValueError("The inputs X, Y should be either Pointclouds objects or tensors.")
+    if pc.dim() != 3:
+        raise ValueError(f"{who}: point sets must be (N, P, D) tensors or Pointclouds")
+    return pc, None, None
+
+
+def _refuse_grad(who, *ts):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise NotImplementedError(f"{who}: not differentiable (an input requires grad; call it under torch.no_grad() "
+                                  "or detach the inputs)")
+
+
+def _split_rts(rts):
+    return SimilarityTransform(rts[..., :9].reshape(*rts.shape[:-1], 3, 3), rts[..., 9:12], rts[..., 12])
+
+
+def corresponding_points_alignment(X, Y, weights=None, estimate_scale: bool = False, allow_reflection: bool = False,
+                                   eps: float = 1e-9):
+    """pytorch3d.ops.corresponding_points_alignment: the similarity transform (R, T, s) minimising
+    sum_i w_i |s X_i R + T - Y_i|^2 per cloud (Umeyama), for (N,P,3) tensors or Pointclouds of equal sizes
+    (their lengths weigh the padding 0). Means, covariance and the 3x3 SVD are float64 on the device
+    (kernels.points_alignment, csrc/mr_points.hip); the result is float32. Not differentiable."""
+    Xt, xc, xl = _clouds_and_lengths(X, "corresponding_points_alignment")
+    Yt, yc, _ = _clouds_and_lengths(Y, "corresponding_points_alignment")
+    counts = xc if xc is not None else [Xt.shape[1]] * Xt.shape[0]
+    if Xt.shape != Yt.shape or counts != (yc if yc is not None else [Yt.shape[1]] * Yt.shape[0]):
+        raise ValueError("Point sets X and Y have to have the same number of batches, points and dimensions.")
+    if weights is not None and tuple(weights.shape) != tuple(Xt.shape[:2]):
+        raise ValueError("weights should have the same first two dimensions as X.")
+    if Xt.shape[2] != 3:
+        raise NotImplementedError("corresponding_points_alignment: only D = 3 is built")
+    _refuse_grad("corresponding_points_alignment", Xt, Yt, weights)
+    if any(c < 4 for c in counts):
+        warnings.warn("The size of one of the point clouds is <= dim+1. "
+                      "corresponding_points_alignment cannot return a unique rotation.")
+    _require_cuda(Xt, Yt, weights)
+    flags = (_lib.MR_ICP_ESTIMATE_SCALE if estimate_scale else 0) | \
+        (_lib.MR_ICP_ALLOW_REFLECTION if allow_reflection else 0)
+    return _split_rts(kernels.points_alignment(Xt, Yt, xl, weights, flags, eps))
+
+
+def iterative_closest_point(X, Y, init_transform=None, max_iterations: int = 100, relative_rmse_thr: float = 1e-6,
+                            estimate_scale: bool = False, allow_reflection: bool = False, verbose: bool = False):
+    """pytorch3d.ops.iterative_closest_point for (N,P,3) tensors or Pointclouds (pytorch3d_icp_registeration.py:
+    154-185): from ``Xt = s X R + T`` (``init_transform`` or the identity), repeat { nearest target of every Xt point;
+    align the ORIGINAL X to those targets; rmse of the new Xt against them } until every cloud's relative rmse drop
+    is <= ``relative_rmse_thr`` (``converged=True``) or ``max_iterations`` have run. Returns
+    ``ICPSolution(converged, rmse (N,), Xt, RTs, t_history)``, ``len(t_history)`` being the iterations run.
+
+    The loop runs on the device, four launches an iteration and no (N, P1, P2) matrix (kernels.icp, csrc/mr_points.hip);
+    the host reads two status words every few iterations. Deterministic; not differentiable."""
+    if verbose:
+        raise NotImplementedError("iterative_closest_point: verbose=True is not built")
+    Xt, xc, xl = _clouds_and_lengths(X, "iterative_closest_point")
+    Yt, yc, yl = _clouds_and_lengths(Y, "iterative_closest_point")
+    b, dim = Xt.shape[0], Xt.shape[2]
+    if dim != Yt.shape[2] or b != Yt.shape[0]:
+        raise ValueError("Point sets X and Y have to have the same number of batches and data dimensions.")
+    if init_transform is not None:
+        try:
+            R, T, s = init_transform
+            assert tuple(R.shape) == (b, dim, dim) and tuple(T.shape) == (b, dim) and tuple(s.shape) == (b,)
+        except Exception:
+            raise ValueError("The initial transformation init_transform has to be a named tuple SimilarityTransform "
+                             "with elements (R, T, s). R are dim x dim orthonormal matrices of shape "
+                             "(minibatch, dim, dim), T is a batch of dim-dimensional translations of shape "
+                             "(minibatch, dim) and s is a batch of scalars of shape (minibatch,).") from None
+    if dim != 3:
+        raise NotImplementedError("iterative_closest_point: only D = 3 is built")
+    _refuse_grad("iterative_closest_point", Xt, Yt, *(init_transform or ()))
+    if yc is not None and any(cy == 0 and cx > 0 for cx, cy in zip(xc or [Xt.shape[1]] * b, yc)):
+        raise ValueError("iterative_closest_point: a target cloud is empty where its source is not")
+    _require_cuda(Xt, Yt, *(init_transform or ()))
+    flags = (_lib.MR_ICP_ESTIMATE_SCALE if estimate_scale else 0) | \
+        (_lib.MR_ICP_ALLOW_REFLECTION if allow_reflection else 0)
+    converged, iters, rmse, xt, rts, hist = kernels.icp(Xt, Yt, xl, yl, init_transform, max_iterations,
+                                                        relative_rmse_thr, flags)
+    if isinstance(X, Pointclouds):
+        xt = X.update_padded(xt)
+    return ICPSolution(converged, rmse, xt, _split_rts(rts), [_split_rts(hist[i]) for i in range(iters)])
 
 
 def _packed_faces(faces_list, Vs):

@@ -1,4 +1,4 @@
-"""PyTorch3D-free ``Meshes`` and textures (the reference passes
+"""PyTorch3D-free ``Meshes``, textures and ``Pointclouds`` (the reference passes
 ``pytorch3d.structures.Meshes`` into every render call: torch_renderer.py:111,156).
 
 A batch built with ``Meshes.extend(N)`` (batch_rendering_test.py:326,
@@ -340,3 +340,104 @@ class Meshes:
             return Meshes([self._verts_list[0]], [self._faces_list[0]], self.textures)
         tex = self.textures[i] if self.textures is not None else None
         return Meshes([self._verts_list[i]], [self._faces_list[i]], tex)
+
+
+class Pointclouds:
+    """Batch of point clouds of different sizes (subset of upstream structures/pointclouds.py used by the
+    registration scripts, pytorch3d_icp_registeration.py:154-185): a list of (P_i, 3) tensors or a padded (N, P, 3)
+    tensor. The per-cloud counts are also kept on the host, so that reading them does not synchronise. Normals and
+    features are not built."""
+
+    def __init__(self, points, normals=None, features=None):
+        if normals is not None or features is not None:
+            raise NotImplementedError("Pointclouds: normals / features are not built")
+        self._padded = None
+        if torch.is_tensor(points):
+            if points.dim() != 3 or points.shape[2] != 3:
+                raise ValueError("Points tensor has incorrect dimensions.")
+            self._list = None
+            self._padded = points
+            self._counts = [int(points.shape[1])] * int(points.shape[0])
+        elif isinstance(points, (list, tuple)):
+            pts = list(points)
+            for p in pts:
+                if not torch.is_tensor(p) or (p.numel() and (p.dim() != 2 or p.shape[1] != 3)):
+                    raise ValueError("Clouds in list must be of shape Px3 or empty")
+                if p.device != pts[0].device:
+                    raise ValueError("All points must be on the same device")
+            self._list = [p if p.numel() else p.reshape(0, 3) for p in pts]
+            self._counts = [int(p.shape[0]) for p in self._list]
+        else:
+            raise ValueError("Points must be either a list or a tensor with shape (batch_size, P, 3)")
+        self._num = None
+
+    def __len__(self):
+        return len(self._counts)
+
+    @property
+    def device(self):
+        if self._padded is not None:
+            return self._padded.device
+        return self._list[0].device if self._list else torch.device("cpu")
+
+    def isempty(self):
+        return len(self) == 0 or all(c == 0 for c in self._counts)
+
+    def counts(self):
+        """The per-cloud point counts as Python ints (host side)."""
+        return list(self._counts)
+
+    def num_points_per_cloud(self):
+        if self._num is None:
+            self._num = torch.tensor(self._counts, dtype=torch.int64, device=self.device)
+        return self._num
+
+    def points_list(self):
+        if self._list is None:
+            self._list = [self._padded[i, :c] for i, c in enumerate(self._counts)]
+        return self._list
+
+    def points_padded(self):
+        if self._padded is None:
+            P = max(self._counts) if self._counts else 0
+            ref = self._list[0] if self._list else torch.zeros(0, 3)
+            out = ref.new_zeros((len(self._list), P, 3))
+            for i, p in enumerate(self._list):
+                out[i, :p.shape[0]] = p
+            self._padded = out
+        return self._padded
+
+    def points_packed(self):
+        pl = self.points_list()
+        return torch.cat(pl, 0) if pl else torch.zeros(0, 3)
+
+    def update_padded(self, new_points_padded):
+        """A Pointclouds of the same sizes whose points are the leading rows of ``new_points_padded`` (N, P, 3)."""
+        if tuple(new_points_padded.shape) != tuple(self.points_padded().shape):
+            raise ValueError("new values must have the same shape as the padded points")
+        pc = Pointclouds.__new__(Pointclouds)
+        pc._counts = list(self._counts)
+        pc._padded = new_points_padded
+        pc._list = [new_points_padded[i, :c] for i, c in enumerate(self._counts)]
+        pc._num = self._num if self._num is not None and self._num.device == new_points_padded.device else None
+        return pc
+
+    def _map(self, fn):
+        pc = Pointclouds.__new__(Pointclouds)
+        pc._counts = list(self._counts)
+        pc._list = None if self._list is None else [fn(p) for p in self._list]
+        pc._padded = None if self._padded is None else fn(self._padded)
+        pc._num = None
+        return pc
+
+    def to(self, device):
+        return self._map(lambda t: t.to(device))
+
+    def cuda(self):
+        return self.to("cuda")
+
+    def clone(self):
+        return self._map(lambda t: t.clone())
+
+    def detach(self):
+        return self._map(lambda t: t.detach())
