@@ -510,6 +510,21 @@ int32_t mr_points_alignment(const float* x, const float* y, int64_t N, int64_t P
                             const float* weights, int32_t flags, double eps, float* rts, void* ws, size_t ws_bytes,
                             void* stream);
 
+/* The chamfer distance of ONE cloud pair under S poses (the pose-search inner loop of chamfer_loss_evaluation.py:
+ * 105-126 and pytorch3d_icp_evaluation.py:158-239): x (P1,3), y (P2,3), rts (S,13) as for ICP above, x' = s (x R) + T
+ * with the ICP code's operation order. out[k] (S) is what mr_chamfer_forward without a batch-reduction flag gives
+ * for the clouds (x' of pose k, y): flags takes MR_CHAMFER_POINT_MEAN and MR_CHAMFER_SINGLE. One launch whose
+ * workgroups each own a pose, a direction and 512 queries and scan every target (x' is formed in registers or while
+ * it is staged: it is never written), then a finalising launch; no memset, no atomics, nothing read by the host.
+ * idx_x (S,P1) / idx_y (S,P2) (each may be NULL; idx_y is not written with MR_CHAMFER_SINGLE): the neighbours, ties to
+ * the lowest index. pose_grad (S,13) or NULL: d out[k] / d (R, T, s) of pose k in rts' layout, from float64 sums in a
+ * fixed order (bitwise reproducible). Large clouds under few poses leave most of the chip idle: that case is
+ * correct, and mr_chamfer_forward on materialised clouds is the faster call for it. */
+size_t mr_posed_chamfer_workspace(int64_t S, int64_t P1, int64_t P2);
+int32_t mr_posed_chamfer(const float* x, const float* y, int64_t P1, int64_t P2, const float* rts, int64_t S,
+                         int32_t norm, int32_t flags, float* out, int32_t* idx_x, int32_t* idx_y, float* pose_grad,
+                         void* ws, size_t ws_bytes, void* stream);
+
 /* Work counters left in `workspace` by the last mr_render_forward / mr_rasterize_meshes that used it
  * (same N, total faces, H, W, max_faces_per_bin). Synchronises `stream`; for benchmarks and tools.
  * out[0] = (tile, face) list entries, out[1] = raster work units, out[2] = non-empty 8x8 tiles,

@@ -159,6 +159,8 @@ _SIGS = [
     ("mr_chamfer_backward_workspace", _SZ, [_I64, _I64, _I64]),
     ("mr_chamfer_backward", _I32, [_VP, _VP, _I64, _I64, _I64, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ,
                                    _VP]),
+    ("mr_posed_chamfer_workspace", _SZ, [_I64, _I64, _I64]),
+    ("mr_posed_chamfer", _I32, [_VP, _VP, _I64, _I64, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     ("mr_icp_workspace", _SZ, [_I64, _I64, _I64]),
     ("mr_icp_init", _I32, [_VP, _I64, _I64, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     ("mr_icp_iterate", _I32, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, _I32, ctypes.c_float, _I32, _I32, _VP, _VP, _VP,

@@ -28,6 +28,8 @@
 //                   Procrustes problem by a fixed-sweep Jacobi SVD in float64, then sums its tile of the residual
 //                   under the new transform) and k_icp_status (rmse, relative drop, the device status words every
 //                   kernel of a later iteration reads first). No float atomics, every sum in a fixed order.
+//   k_posed_*       the chamfer distance of ONE cloud pair under S poses (mr_posed_chamfer): k_posed_nn, a workgroup
+//                   per (pose, direction, 512 queries) that scans all targets itself, and k_posed_final (see there).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -865,9 +867,253 @@ __global__ void __launch_bounds__(MRR_BLOCK) k_icp_apply(const float* __restrict
   o[2] = o2;
 }
 
+// ---------------------------------------------------------------------------
+// Chamfer distance of ONE cloud pair under S rigid / similarity poses (mr_posed_chamfer): x' = s (x R) + T per pose.
+// ---------------------------------------------------------------------------
+#define MRP_MOM 13      // per-workgroup pose moments (double): sum g (3), sum x^T g (9, row = x component), sum (x R).g
+
+struct PosedWS {
+  double* part;   // (2, S, ntile) distance sums of a workgroup's queries
+  double* mom;    // (2, S, ntile, MRP_MOM)
+  int64_t ntile;  // query tiles of the larger cloud
+  size_t bytes;
+};
+PosedWS carve_posed(void* base, int64_t S, int64_t P1, int64_t P2) {
+  PosedWS w;
+  Carver c(base);
+  w.ntile = ceil_div(P1 > P2 ? P1 : P2, MRN_QT);
+  w.part = c.take<double>(2 * (size_t)(S * w.ntile));
+  w.mom = c.take<double>(2 * (size_t)(S * w.ntile) * MRP_MOM);
+  w.bytes = c.off;
+  return w;
+}
+
+// block_sums for a k_nn-sized workgroup (MRN_BLOCK = 128 threads, two waves): the butterfly inside each wave, then
+// wave 0 + wave 1. sm: 2 * K doubles. Every thread gets the totals.
+template <int K> __device__ __forceinline__ void tile_sums(double (&v)[K], double* sm) {
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) sm[(threadIdx.x >> 6) * K + k] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = sm[k] + sm[K + k];
+  __syncthreads();
+}
+
+// grid (query tiles of the larger cloud, S, directions). A workgroup owns one pose, one direction and one tile of
+// 512 queries and scans ALL targets itself, in ascending LDS chunks: with the strict < its minimum is final and
+// ties go to the lowest index, so there is no key buffer, memset, atomic or decode pass. Direction 0: queries x'
+// (x transformed in registers, as k_icp_nn), targets y. Direction 1: queries y, targets x' transformed while they
+// are staged: the same sim_apply, so both directions see the bits a materialised cloud would hold. Outputs per
+// workgroup: idx (optional), the float64 sum of its queries' distances, and (mom != NULL) the pose moments with
+// g = x' - y of every pair (sign(.) for norm 1) and x the pair's untransformed source point.
+template <int NORM>
+__global__ void __launch_bounds__(MRN_BLOCK) k_posed_nn(const float* __restrict__ x, const float* __restrict__ y,
+                                                        int64_t P1, int64_t P2, const float* __restrict__ rts,
+                                                        int64_t S, int64_t ntile, int32_t* __restrict__ idx_x,
+                                                        int32_t* __restrict__ idx_y, double* __restrict__ part,
+                                                        double* __restrict__ mom) {
+  __shared__ float4 sm[MRN_MAXCHUNK];
+  __shared__ double red[2 * MRP_MOM];
+  const int d = blockIdx.z;
+  const int64_t n = blockIdx.y;
+  const int64_t Pq = d ? P2 : P1, Pt = d ? P1 : P2;
+  const int64_t q0 = (int64_t)blockIdx.x * MRN_QT;
+  if (q0 >= Pq) return;  // uniform over the workgroup
+  const float* __restrict__ q = d ? y : x;
+  const float* __restrict__ t = d ? x : y;
+  const float* __restrict__ tr = rts + n * MRI_RTS;
+
+  float qx[MRN_Q], qy[MRN_Q], qz[MRN_Q], best[MRN_Q];
+  int bi[MRN_Q];
+#pragma unroll
+  for (int k = 0; k < MRN_Q; ++k) {
+    const int64_t i = q0 + k * MRN_BLOCK + threadIdx.x;
+    const bool ok = i < Pq;
+    const float a0 = ok ? q[3 * i] : 0.0f, a1 = ok ? q[3 * i + 1] : 0.0f, a2 = ok ? q[3 * i + 2] : 0.0f;
+    if (d == 0) {
+      sim_apply(tr, a0, a1, a2, qx[k], qy[k], qz[k]);
+    } else {
+      qx[k] = a0;
+      qy[k] = a1;
+      qz[k] = a2;
+    }
+    best[k] = __builtin_inff();
+    bi[k] = 0;
+  }
+  for (int64_t t0 = 0; t0 < Pt; t0 += MRN_MAXCHUNK) {
+    const int cnt = (int)((Pt - t0 < MRN_MAXCHUNK) ? Pt - t0 : MRN_MAXCHUNK);
+    if (t0) __syncthreads();  // the previous chunk has been read
+    for (int j = threadIdx.x; j < cnt; j += MRN_BLOCK) {
+      const float* p = t + 3 * (t0 + j);
+      float p0 = p[0], p1 = p[1], p2 = p[2];
+      if (d) sim_apply(tr, p0, p1, p2, p0, p1, p2);
+      sm[j] = make_float4(p0, p1, p2, 0.0f);
+    }
+    __syncthreads();
+    const int base = (int)t0;
+#pragma unroll 4
+    for (int j = 0; j < cnt; ++j) {
+      const float4 p = sm[j];
+#pragma unroll
+      for (int k = 0; k < MRN_Q; ++k) {
+        const float dd = dist3<NORM>(qx[k], qy[k], qz[k], p);
+        if (dd < best[k]) {  // strict, ascending chunks: the lowest index wins a tie
+          best[k] = dd;
+          bi[k] = base + j;
+        }
+      }
+    }
+  }
+
+  int32_t* __restrict__ idx = d ? idx_y : idx_x;
+  double a[MRP_MOM];
+#pragma unroll
+  for (int k = 0; k < MRP_MOM; ++k) a[k] = 0.0;
+  double dsum = 0.0;
+#pragma unroll
+  for (int k = 0; k < MRN_Q; ++k) {
+    const int64_t i = q0 + k * MRN_BLOCK + threadIdx.x;
+    if (i >= Pq) continue;
+    if (idx) idx[n * Pq + i] = bi[k];
+    dsum += (double)best[k];
+    if (!mom) continue;
+    // the pair's source point (untransformed), its image x' and the point of y
+    const float* __restrict__ sp = x + 3 * (d ? (int64_t)bi[k] : i);
+    const float s0 = sp[0], s1 = sp[1], s2 = sp[2];
+    float g0, g1, g2;
+    if (d == 0) {
+      const float* __restrict__ tp = y + 3 * (int64_t)bi[k];
+      g0 = qx[k] - tp[0];
+      g1 = qy[k] - tp[1];
+      g2 = qz[k] - tp[2];
+    } else {
+      float o0, o1, o2;
+      sim_apply(tr, s0, s1, s2, o0, o1, o2);
+      g0 = o0 - qx[k];
+      g1 = o1 - qy[k];
+      g2 = o2 - qz[k];
+    }
+    if (NORM == 1) {
+      g0 = sgn(g0);
+      g1 = sgn(g1);
+      g2 = sgn(g2);
+    }
+    const double e0 = (double)g0, e1 = (double)g1, e2 = (double)g2;
+    const double x0 = (double)s0, x1 = (double)s1, x2 = (double)s2;
+    a[0] += e0;
+    a[1] += e1;
+    a[2] += e2;
+    a[3] += x0 * e0;
+    a[4] += x0 * e1;
+    a[5] += x0 * e2;
+    a[6] += x1 * e0;
+    a[7] += x1 * e1;
+    a[8] += x1 * e2;
+    a[9] += x2 * e0;
+    a[10] += x2 * e1;
+    a[11] += x2 * e2;
+    const double r0 = (x0 * (double)tr[0] + x1 * (double)tr[3]) + x2 * (double)tr[6];
+    const double r1 = (x0 * (double)tr[1] + x1 * (double)tr[4]) + x2 * (double)tr[7];
+    const double r2 = (x0 * (double)tr[2] + x1 * (double)tr[5]) + x2 * (double)tr[8];
+    a[12] += (r0 * e0 + r1 * e1) + r2 * e2;
+  }
+  const int64_t slot = ((int64_t)d * S + n) * ntile + blockIdx.x;
+  {
+    double one[1] = {dsum};
+    tile_sums<1>(one, red);
+    if (threadIdx.x == 0) part[slot] = one[0];
+  }
+  if (!mom) return;  // uniform
+  tile_sums<MRP_MOM>(a, red);
+  if (threadIdx.x < MRP_MOM) {
+    double v = 0.0;
+#pragma unroll
+    for (int k = 0; k < MRP_MOM; ++k) v = threadIdx.x == k ? a[k] : v;
+    mom[slot * MRP_MOM + threadIdx.x] = v;
+  }
+}
+
+// Thread n finishes pose n: its tiles' partials in order, the point reduction, x -> y plus y -> x (x -> y alone with
+// MR_CHAMFER_SINGLE) as k_cham_final does; pose_grad (S, 13; may be NULL) = d out[n] / d (R, T, s) in rts' layout
+// from the moments: dT = k sum_d c_d sum g, dR = k s sum_d c_d sum x^T g, ds = k sum_d c_d sum (x R).g, k = 2 or 1.
+__global__ void __launch_bounds__(MRR_BLOCK) k_posed_final(const double* __restrict__ part,
+                                                           const double* __restrict__ mom, int64_t ntile, int64_t S,
+                                                           int64_t P1, int64_t P2, const float* __restrict__ rts,
+                                                           int norm, int flags, float* __restrict__ out,
+                                                           float* __restrict__ pose_grad) {
+  const int64_t n = (int64_t)blockIdx.x * MRR_BLOCK + threadIdx.x;
+  if (n >= S) return;
+  const bool single = flags & MR_CHAMFER_SINGLE, pmean = flags & MR_CHAMFER_POINT_MEAN;
+  double v = 0.0;
+  double m[MRP_MOM];
+#pragma unroll
+  for (int k = 0; k < MRP_MOM; ++k) m[k] = 0.0;
+  for (int d = 0; d < (single ? 1 : 2); ++d) {
+    const int64_t Pq = d ? P2 : P1;
+    const int64_t tiles = (Pq + MRN_QT - 1) / MRN_QT;
+    const double c = pmean ? 1.0 / (double)(Pq > 1 ? Pq : 1) : 1.0;
+    const int64_t slot = ((int64_t)d * S + n) * ntile;
+    double s = 0.0;
+    for (int64_t b = 0; b < tiles; ++b) s += part[slot + b];
+    v += c * s;
+    if (pose_grad) {
+      double md[MRP_MOM];
+#pragma unroll
+      for (int k = 0; k < MRP_MOM; ++k) md[k] = 0.0;
+      for (int64_t b = 0; b < tiles; ++b)
+#pragma unroll
+        for (int k = 0; k < MRP_MOM; ++k) md[k] += mom[(slot + b) * MRP_MOM + k];
+#pragma unroll
+      for (int k = 0; k < MRP_MOM; ++k) m[k] += c * md[k];
+    }
+  }
+  out[n] = (float)v;
+  if (!pose_grad) return;
+  const double kf = norm == 2 ? 2.0 : 1.0;
+  const double ks = kf * (double)rts[n * MRI_RTS + 12];
+  float* __restrict__ o = pose_grad + n * MRI_RTS;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) o[k] = (float)(ks * m[3 + k]);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) o[9 + k] = (float)(kf * m[k]);
+  o[12] = (float)(kf * m[12]);
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t mr_posed_chamfer_workspace(int64_t S, int64_t P1, int64_t P2) {
+  if (!sizes_ok(S, P1, P2)) return 0;
+  return carve_posed(nullptr, S, P1, P2).bytes;
+}
+
+int32_t mr_posed_chamfer(const float* x, const float* y, int64_t P1, int64_t P2, const float* rts, int64_t S,
+                         int32_t norm, int32_t flags, float* out, int32_t* idx_x, int32_t* idx_y, float* pose_grad,
+                         void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = check_clouds("posed chamfer", x, y, S, P1, P2, norm)) return rc;
+  if (flags & ~(MR_CHAMFER_POINT_MEAN | MR_CHAMFER_SINGLE))
+    return set_err(MR_EINVAL, "posed chamfer: flags takes MR_CHAMFER_POINT_MEAN and MR_CHAMFER_SINGLE only");
+  if (!rts || !out || !ws) return set_err(MR_EINVAL, "posed chamfer: rts / out / workspace is NULL");
+  const PosedWS w = carve_posed(ws, S, P1, P2);
+  if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "posed chamfer workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  const bool single = flags & MR_CHAMFER_SINGLE;
+  // a single-directional call scans (and writes idx for) x -> y alone: its grid covers the tiles of x
+  const int64_t gx = single ? (int64_t)ceil_div(P1, MRN_QT) : w.ntile;
+  const dim3 grid((unsigned)gx, (unsigned)S, single ? 1u : 2u);
+  double* mom = pose_grad ? w.mom : nullptr;
+  if (int rc = launch(KID_NONE, "k_posed_nn", norm == 2 ? k_posed_nn<2> : k_posed_nn<1>, grid, MRN_BLOCK, 0, st, x, y, P1, P2,
+                      rts, S, w.ntile, idx_x, idx_y, w.part, mom))
+    return rc;
+  return launch(KID_NONE, "k_posed_final", k_posed_final, (unsigned)ceil_div(S, MRR_BLOCK), MRR_BLOCK, 0, st,
+                (const double*)w.part, (const double*)mom, w.ntile, S, P1, P2, rts, (int)norm, (int)flags, out, pose_grad);
+}
 
 size_t mr_nearest_points_workspace(int64_t N, int64_t P1, int64_t P2) {
   if (!sizes_ok(N, P1, P2)) return 0;

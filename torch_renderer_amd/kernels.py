@@ -314,6 +314,109 @@ class ChamferDistance(torch.autograd.Function):
         return gx.to(xdt), gy.to(ydt), None, None, None, None, None
 
 
+def _one_cloud(t, name):
+    """A (P,3) or (1,P,3) cloud as a contiguous float32 (P,3) tensor."""
+    if t.dim() == 3 and t.shape[0] == 1:
+        t = t[0]
+    if t.dim() != 2:
+        raise ValueError(f"posed chamfer: {name} must be one cloud, (P, 3) or (1, P, 3)")
+    if t.shape[1] != 3:
+        raise NotImplementedError("posed chamfer: only D = 3 is built")
+    if t.shape[0] < 1:
+        raise ValueError(f"posed chamfer: {name} is empty")
+    return t.detach().float().contiguous()
+
+
+def _pose_args(R, T, s):
+    """(R (S,3,3), T (S,3), s (S,) or None) checked; T may come as (S,1,3)."""
+    if R.dim() != 3 or tuple(R.shape[1:]) != (3, 3):
+        raise ValueError("posed chamfer: R must be (S, 3, 3)")
+    S = R.shape[0]
+    if S < 1:
+        raise ValueError("posed chamfer: at least one pose is needed")
+    if tuple(T.shape) not in ((S, 3), (S, 1, 3)):
+        raise ValueError("posed chamfer: T must be (S, 3) or (S, 1, 3) with R's S")
+    if s is not None and tuple(s.shape) != (S,):
+        raise ValueError("posed chamfer: s must be (S,) with R's S")
+    return S
+
+
+def _pack_rts(R, T, s):
+    """(S,13) float32 rows (R row-major, T, s): one cat launch (a non-contiguous R is gathered by it)."""
+    S = R.shape[0]
+    sc = R.new_ones((S, 1), dtype=torch.float32) if s is None else s.detach().float().reshape(S, 1)
+    return torch.cat((R.detach().float().reshape(S, 9), T.detach().float().reshape(S, 3), sc), 1)
+
+
+def _posed_chamfer_launch(xf, yf, rts, norm, flags, want_idx, want_grad):
+    L = _lib.load()
+    dev = xf.device
+    S, P1, P2 = rts.shape[0], xf.shape[0], yf.shape[0]
+    single = bool(flags & _lib.MR_CHAMFER_SINGLE)
+    out = torch.empty(S, device=dev)
+    ix = torch.empty((S, P1), dtype=torch.int32, device=dev) if want_idx else None
+    iy = torch.empty((S, P2), dtype=torch.int32, device=dev) if want_idx and not single else None
+    pg = torch.empty((S, 13), device=dev) if want_grad else None
+    wsb = _ws_size(L.mr_posed_chamfer_workspace, S, P1, P2)
+    if wsb == 0:
+        raise NotImplementedError("mi355r: posed chamfer: more than 65535 poses or clouds too large for 32-bit point ids")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    check(L.mr_posed_chamfer(ptr(xf), ptr(yf), P1, P2, ptr(rts), S, int(norm), int(flags), ptr(out), ptr(ix), ptr(iy),
+                             ptr(pg), ptr(ws), wsb, _lib.stream_handle(dev)))
+    return out, ix, iy, pg
+
+
+def posed_chamfer(x, y, R, T, s=None, norm=2, flags=_lib.MR_CHAMFER_POINT_MEAN, return_idx=False, return_grad=False):
+    """The chamfer distance of ONE cloud pair under S poses, x' = s (x R) + T with row vectors (mr_posed_chamfer):
+    out (S,) float32, what ``ChamferDistance`` without a batch reduction gives for the materialised clouds
+    (x' of pose k, y). ``flags``: MR_CHAMFER_POINT_MEAN | MR_CHAMFER_SINGLE. With ``return_idx`` also the neighbours
+    idx_x (S,P1) and idx_y (S,P2; None with MR_CHAMFER_SINGLE) as int32, ties to the lowest index; with
+    ``return_grad`` also pose_grad (S,13) = d out[k] / d (R row-major, T, s). No autograd (``PosedChamfer`` is the
+    node); two launches after one cat that packs the poses, nothing synchronises.
+    Returns out, or (out, idx_x, idx_y[, pose_grad]) / (out, pose_grad)."""
+    if norm not in (1, 2):
+        raise ValueError("Support for 1 or 2 norm.")
+    xf, yf = _one_cloud(x, "x"), _one_cloud(y, "y")
+    _pose_args(R, T, s)
+    _require_cuda(xf, yf, R, T, s)
+    out, ix, iy, pg = _posed_chamfer_launch(xf, yf, _pack_rts(R, T, s), norm, flags, return_idx, return_grad)
+    if not return_idx and not return_grad:
+        return out
+    return (out,) + ((ix, iy) if return_idx else ()) + ((pg,) if return_grad else ())
+
+
+class PosedChamfer(torch.autograd.Function):
+    """``posed_chamfer`` as an autograd node over (R, T, s): the forward leaves d out[k] / d pose k (S,13), computed
+    from 13 float64 moments per workgroup in a fixed order, and the backward is that times the upstream (S,)
+    gradient: one multiply. The clouds are constants. ``s`` may be None."""
+
+    @staticmethod
+    def forward(ctx, x, y, R, T, s, flags, norm):
+        xf, yf = _one_cloud(x, "x"), _one_cloud(y, "y")
+        _pose_args(R, T, s)
+        _require_cuda(xf, yf, R, T, s)
+        want = bool(ctx.needs_input_grad[2] or ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
+        out, _, _, pg = _posed_chamfer_launch(xf, yf, _pack_rts(R, T, s), norm, flags, False, want)
+        ctx.set_materialize_grads(False)
+        if want:
+            ctx.save_for_backward(pg)
+            ctx.args = (R.dtype, T.dtype, tuple(T.shape), None if s is None else s.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return (None,) * 7
+        (pg,) = ctx.saved_tensors
+        rdt, tdt, tshape, sdt = ctx.args
+        need = ctx.needs_input_grad
+        gp = g.detach().float()[:, None] * pg
+        gR = gp[:, :9].reshape(-1, 3, 3).to(rdt) if need[2] else None
+        gT = gp[:, 9:12].reshape(tshape).to(tdt) if need[3] else None
+        gs = gp[:, 12].to(sdt) if need[4] and sdt is not None else None
+        return None, None, gR, gT, gs, None, None
+
+
 # Iterations enqueued between two reads of the device status: a read costs ~14 us, an iteration enqueued after
 # convergence ~18 us (tools/icp_bench.py, DESIGN.md §3, ICP)
 ICP_STATUS_BATCH = 8

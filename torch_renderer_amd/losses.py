@@ -4,6 +4,9 @@ Chamfer distance (``pytorch3d.loss.chamfer_distance`` as the geometry-fitting lo
 mesh_deformer.py:299-352, deform_mesh_from_pcd.py:160-212, and on whole clouds, chamfer_loss_evaluation.py:126):
 ``chamfer_distance`` is one autograd node over a tiled nearest-neighbour kernel that keeps the targets in LDS and
 never writes the (N, P1, P2) distance matrix (kernels.ChamferDistance, csrc/mr_points.hip). Deterministic.
+``posed_chamfer_distance`` scores S pose hypotheses of ONE cloud pair (the inner loop of chamfer_loss_evaluation.py:
+105-126 and pytorch3d_icp_evaluation.py:158-239) in one fused pass that never materialises the S transformed clouds,
+with gradients to the poses (kernels.PosedChamfer).
 
 Mesh shape priors (``pytorch3d.loss.mesh_edge_loss`` / ``mesh_laplacian_smoothing`` / ``mesh_normal_consistency``,
 called together by update_mesh_shape_prior_losses at deform_mesh_with_color.py:248-256 and mesh_deformer.py:
@@ -37,7 +40,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .kernels import ChamferDistance, MeshShapePriors, _require_cuda, mesh_prior_topology
+from .kernels import ChamferDistance, MeshShapePriors, PosedChamfer, _require_cuda, mesh_prior_topology
 from .structures import Pointclouds
 
 
@@ -179,3 +182,41 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_nor
         {None: 0, "mean": _lib.MR_CHAMFER_BATCH_MEAN, "sum": _lib.MR_CHAMFER_BATCH_SUM}[batch_reduction] | \
         (_lib.MR_CHAMFER_SINGLE if single_directional else 0)
     return ChamferDistance.apply(x, y, x_lengths, y_lengths, weights, flags, norm), None
+
+
+def posed_chamfer_distance(x, y, R, T=None, s=None, *, norm: int = 2, point_reduction="mean",
+                           single_directional: bool = False):
+    """The chamfer distance of ONE source cloud ``x`` ((P1,3) or (1,P1,3)) to ONE target cloud ``y`` ((P2,3) or
+    (1,P2,3)) under S pose hypotheses, as (S,) float32: entry k is
+    ``chamfer_distance((s[k] * x[None] @ R[k] + T[k]), y[None], batch_reduction=None, norm=..., point_reduction=...,
+    single_directional=...)[0]``, without the S copies of either cloud.
+
+    ``R (S,3,3)`` (any strides), ``T (S,3)`` or ``(S,1,3)`` and the optional scale ``s (S,)`` follow the library's
+    row-vector convention ``x' = s (x R) + T`` of ``SimilarityTransform`` and ``ICPSolution.RTs``; an ``(R, T, s)``
+    triple may be passed in place of ``R``. The reference scripts' ``transform_pcd_tensors(pcds, ts, Rs)`` applies
+    column-vector rotations ``Rs @ p``: pass ``R = Rs.transpose(1, 2)`` (and ``T = ts``).
+
+    Differentiable w.r.t. ``R``, ``T`` and ``s`` (bitwise reproducible; through ``transforms.euler_angles_to_matrix``
+    also w.r.t. Euler angles); the clouds are constants, and one that requires grad while grad mode is on raises
+    NotImplementedError. The kernel is built for many poses of small clouds; a large cloud under a handful of poses
+    is computed correctly but leaves most of the chip idle (materialise the clouds and call ``chamfer_distance``
+    there: nothing routes automatically)."""
+    if isinstance(R, (tuple, list)):
+        if len(R) != 3 or T is not None or s is not None:
+            raise ValueError("posed_chamfer_distance: pass either R, T[, s] or one (R, T, s) triple")
+        R, T, s = R
+    if T is None:
+        raise ValueError("posed_chamfer_distance: T is missing")
+    if norm not in (1, 2):
+        raise ValueError("Support for 1 or 2 norm.")
+    if point_reduction not in ("mean", "sum"):
+        raise ValueError('point_reduction must be one of ["mean", "sum"]')
+    for t in (x, y, R, T):
+        if not torch.is_tensor(t):
+            raise ValueError("posed_chamfer_distance: x, y, R and T are tensors")
+    if torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
+        raise NotImplementedError("posed_chamfer_distance: not differentiable w.r.t. the clouds (x or y requires "
+                                  "grad; detach them: the gradients go to R, T and s)")
+    flags = (_lib.MR_CHAMFER_POINT_MEAN if point_reduction == "mean" else 0) | \
+        (_lib.MR_CHAMFER_SINGLE if single_directional else 0)
+    return PosedChamfer.apply(x, y, R, T, s, flags, norm)

@@ -37,6 +37,40 @@ def quaternion_to_matrix_torch(quaternions: torch.Tensor) -> torch.Tensor:
     return o.reshape(quaternions.shape[:-1] + (3, 3))
 
 
+def _axis_rotation(axis: str, angle: torch.Tensor) -> torch.Tensor:
+    """(..., 3, 3) rotation about one axis: X [[1,0,0],[0,c,-s],[0,s,c]], Y [[c,0,s],[0,1,0],[-s,0,c]],
+    Z [[c,-s,0],[s,c,0],[0,0,1]]."""
+    c, s = torch.cos(angle), torch.sin(angle)
+    one, zero = torch.ones_like(angle), torch.zeros_like(angle)
+    if axis == "X":
+        flat = (one, zero, zero, zero, c, -s, zero, s, c)
+    elif axis == "Y":
+        flat = (c, zero, s, zero, one, zero, -s, zero, c)
+    elif axis == "Z":
+        flat = (c, -s, zero, s, c, zero, zero, zero, one)
+    else:
+        raise ValueError("letter must be either X, Y or Z.")
+    return torch.stack(flat, -1).reshape(angle.shape + (3, 3))
+
+
+def euler_angles_to_matrix(euler_angles: torch.Tensor, convention: str) -> torch.Tensor:
+    """Euler angles in radians (..., 3) -> rotation matrices (..., 3, 3) (upstream
+    pytorch3d.transforms.euler_angles_to_matrix): R = A0(a0) @ A1(a1) @ A2(a2) for the three letters of
+    ``convention`` (any of the 12 orders of X, Y, Z without equal neighbours). Torch ops on any device and dtype,
+    differentiable (chamfer_loss_evaluation.py:105 and pytorch3d_icp_evaluation.py:158 call it with "XYZ")."""
+    if euler_angles.dim() == 0 or euler_angles.shape[-1] != 3:
+        raise ValueError("Invalid input euler angles.")
+    if len(convention) != 3:
+        raise ValueError("Convention must have 3 letters.")
+    if convention[1] in (convention[0], convention[2]):
+        raise ValueError(f"Invalid convention {convention}.")
+    for letter in convention:
+        if letter not in ("X", "Y", "Z"):
+            raise ValueError(f"Invalid letter {letter} in convention string.")
+    a, b, c = (_axis_rotation(l, e) for l, e in zip(convention, torch.unbind(euler_angles, -1)))
+    return torch.matmul(torch.matmul(a, b), c)
+
+
 def _sqrt_positive_part(x: torch.Tensor) -> torch.Tensor:
     ret = torch.zeros_like(x)
     pos = x > 0
