@@ -525,6 +525,60 @@ int32_t mr_posed_chamfer(const float* x, const float* y, int64_t P1, int64_t P2,
                          int32_t norm, int32_t flags, float* out, int32_t* idx_x, int32_t* idx_y, float* pose_grad,
                          void* ws, size_t ws_bytes, void* stream);
 
+/* Point-cloud rendering (PyTorch3D rasterize_points with naive semantics, alpha_composite, norm_weighted_sum).
+ *
+ * mr_rasterize_points: points (total_points,3) hold NDC x, NDC y and view z; view n draws rows first[n] ..
+ * first[n] + count[n] - 1 (several views may name the same rows). Pixel centres are the mesh rasterizer's. Point p
+ * covers a pixel iff z >= 0 and d2 = dx*dx + dy*dy < r*r (float32, dx = x - x_pixel, strict); r = radius, or
+ * radius_per_point[row] when that is not NULL. A pixel keeps the K <= 50 covering points of smallest (z, row),
+ * ascending: idx (N,H,W,K) = idx_base[n] + (row - first[n]) (idx_base NULL: the row), zbuf, dists = d2; -1 in empty
+ * slots. Points with a NaN coordinate are not drawn. No workspace and no capacity: every (view, tile) scans its
+ * view's cloud in chunks of mr_point_raster_chunk() points, so the results depend on no setting.
+ * mr_rasterize_points_backward: grad_points (total_points,3) += (grad_dists 2 dx, grad_dists 2 dy, grad_zbuf) of every
+ * filled slot (either gradient may be NULL), summed with 64-bit fixed-point atomics: bitwise reproducible. */
+int32_t mr_point_raster_chunk(void);
+int32_t mr_rasterize_points(const float* points, const int64_t* first, const int64_t* count, const int64_t* idx_base,
+                            int64_t N, int64_t total_points, int32_t H, int32_t W, float radius,
+                            const float* radius_per_point, int32_t K, int64_t* idx, float* zbuf, float* dists,
+                            void* stream);
+size_t mr_rasterize_points_backward_workspace(int64_t total_points);
+int32_t mr_rasterize_points_backward(const float* points, const int64_t* first, const int64_t* idx_base, int64_t N,
+                                     int64_t total_points, int32_t H, int32_t W, int32_t K, const int64_t* idx,
+                                     const float* grad_zbuf, const float* grad_dists, float* grad_points, void* ws,
+                                     size_t ws_bytes, void* stream);
+
+/* PointsRasterizer.transform: view n projects the world points src_first[n] .. + count[n] - 1 of points (rows may be
+ * shared between views) to out rows dst_first[n] ..: (ax (x / z) + bx, ay (y / z) + by, z) of X R + T, views (N,16)
+ * = R (9), T (3), ax, bx, ay, by, the operand order of mr_project_faces. The backward gives grad_points
+ * (total_points,3), summed over the views through fixed-point atomics, and grad_views (N,12) = d / d (R, T) from
+ * float64 sums in a fixed order. */
+int32_t mr_project_points(const float* points, const int64_t* src_first, const int64_t* dst_first,
+                          const int64_t* count, int64_t N, int64_t max_count, const float* views, float* out,
+                          void* stream);
+size_t mr_project_points_backward_workspace(int64_t total_points);
+int32_t mr_project_points_backward(const float* points, const int64_t* src_first, const int64_t* dst_first,
+                                   const int64_t* count, int64_t N, int64_t total_points, const float* views,
+                                   const float* grad_ndc, float* grad_points, float* grad_views, void* ws,
+                                   size_t ws_bytes, void* stream);
+
+/* Compositing of K-deep point fragments: idx / vals (N,H,W,K), feats (P,C), out (N,H,W,C). Slots with idx < 0 are
+ * skipped; the feature row of a slot is idx - feat_sub[n] (feat_sub NULL: idx). alpha = vals, or with
+ * MR_COMPOSITE_DISTS 1 - vals / r^2 (r = radius, or radius_per_point[idx] of n_radius entries). Default: alpha
+ * compositing, out_c = sum_k f_c alpha_k prod_{j<k} (1 - alpha_j); MR_COMPOSITE_NORM: sum_k f_c alpha_k /
+ * max(sum_k alpha_k, 1e-4). background (C) or NULL: the colour of every pixel whose first slot is empty. The backward
+ * writes grad_vals (N,H,W,K) and grad_feats (P,C), the latter through fixed-point atomics. */
+enum { MR_COMPOSITE_NORM = 1, MR_COMPOSITE_DISTS = 2 };
+int32_t mr_composite_points_forward(const int64_t* idx, const float* vals, const float* feats, int64_t N, int32_t H,
+                                    int32_t W, int32_t K, int32_t C, int64_t P, int32_t flags, float radius,
+                                    const float* radius_per_point, int64_t n_radius, const int64_t* feat_sub,
+                                    const float* background, float* out, void* stream);
+size_t mr_composite_points_backward_workspace(int64_t P, int32_t C);
+int32_t mr_composite_points_backward(const int64_t* idx, const float* vals, const float* feats, int64_t N, int32_t H,
+                                     int32_t W, int32_t K, int32_t C, int64_t P, int32_t flags, float radius,
+                                     const float* radius_per_point, int64_t n_radius, const int64_t* feat_sub,
+                                     const float* background, const float* grad_out, float* grad_vals,
+                                     float* grad_feats, void* ws, size_t ws_bytes, void* stream);
+
 /* Work counters left in `workspace` by the last mr_render_forward / mr_rasterize_meshes that used it
  * (same N, total faces, H, W, max_faces_per_bin). Synchronises `stream`; for benchmarks and tools.
  * out[0] = (tile, face) list entries, out[1] = raster work units, out[2] = non-empty 8x8 tiles,

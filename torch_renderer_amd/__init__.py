@@ -10,3 +10,5 @@ __version__ = "0.1.0"
 from .mesh_renderer import (RasterizationSettings, MeshRasterizer, MeshRenderer, Fragments, rasterize,  # noqa: F401
                             PointLights, AmbientLights, Materials, BlendParams, SoftPhongShader,
                             SoftSilhouetteShader, HardPhongShader)
+from .points_renderer import (PointsRasterizationSettings, PointsRasterizer, PointsRenderer, PointFragments,  # noqa: F401
+                              AlphaCompositor, NormWeightedCompositor, alpha_composite, norm_weighted_sum)

@@ -32,6 +32,7 @@ MR_GRAD_ROWS_CLEARED = 16  # mr_render_backward: first backward over a forward (
 MR_PRIOR_EDGE, MR_PRIOR_LAPLACIAN, MR_PRIOR_NORMAL, MR_PRIOR_ALL = 1, 2, 4, 7  # mr_mesh_priors_*: terms mask
 MR_CHAMFER_POINT_MEAN, MR_CHAMFER_BATCH_MEAN, MR_CHAMFER_BATCH_SUM, MR_CHAMFER_SINGLE = 1, 2, 4, 8  # mr_chamfer_*: flags
 MR_ICP_ESTIMATE_SCALE, MR_ICP_ALLOW_REFLECTION = 1, 2  # mr_icp_iterate / mr_points_alignment: flags
+MR_COMPOSITE_NORM, MR_COMPOSITE_DISTS = 1, 2  # mr_composite_points_*: flags
 
 
 class MrView(ctypes.Structure):
@@ -172,6 +173,20 @@ _SIGS = [
     ("mr_sample_points_backward_workspace", _SZ, [_I64]),
     ("mr_sample_points_backward", _I32, [_I64, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _SZ, _VP]),
     ("mr_face_areas", _I32, [_VP, _I64, _VP, _I64, _VP, _VP]),
+    ("mr_point_raster_chunk", _I32, []),
+    ("mr_rasterize_points", _I32, [_VP, _VP, _VP, _VP, _I64, _I64, _I32, _I32, ctypes.c_float, _VP, _I32, _VP, _VP, _VP,
+                                   _VP]),
+    ("mr_rasterize_points_backward_workspace", _SZ, [_I64]),
+    ("mr_rasterize_points_backward", _I32, [_VP, _VP, _VP, _I64, _I64, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _SZ,
+                                            _VP]),
+    ("mr_project_points", _I32, [_VP, _VP, _VP, _VP, _I64, _I64, _VP, _VP, _VP]),
+    ("mr_project_points_backward_workspace", _SZ, [_I64]),
+    ("mr_project_points_backward", _I32, [_VP, _VP, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    ("mr_composite_points_forward", _I32, [_VP, _VP, _VP, _I64, _I32, _I32, _I32, _I32, _I64, _I32, ctypes.c_float, _VP,
+                                           _I64, _VP, _VP, _VP, _VP]),
+    ("mr_composite_points_backward_workspace", _SZ, [_I64, _I32]),
+    ("mr_composite_points_backward", _I32, [_VP, _VP, _VP, _I64, _I32, _I32, _I32, _I32, _I64, _I32, ctypes.c_float, _VP,
+                                            _I64, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     ("mr_workspace_stats", _I32, [_VP, _I64, _I64, _I32, _I32, _I32, _VP, _VP]),
     ("mr_workspace_counters", _I32, [_VP, _I64, _I64, _I32, _I32, _I32, _VP, _VP]),
     ("mr_per_view_binning", _I32, [_I64, _I64, _I32, _I32]),

@@ -1157,3 +1157,162 @@ class ShadeFragments(torch.autograd.Function):
         if gm is not None and ctx.map_shape[-1] > 3:
             gm = torch.cat([gmap[..., :3], torch.zeros(ctx.map_shape[:2] + (ctx.map_shape[-1] - 3,), device=dev)], -1)
         return gz, gb, gd, gv, gc, gm, guv, None, None, None, None, None, None
+
+
+# --------------------------------------------------------------------------- point clouds: project, rasterize, composite
+def point_raster_chunk() -> int:
+    """Points the point rasterizer stages per pass (its results do not depend on it; tests size clouds around it)."""
+    return int(_lib.load().mr_point_raster_chunk())
+
+
+def _radius_args(radius, rows, what):
+    """(float radius, per-point tensor or None) of a radius given as a number or a (rows,) tensor."""
+    if not torch.is_tensor(radius):
+        return float(radius), None
+    if radius.requires_grad:
+        raise NotImplementedError(f"{what}: a per-point radius that requires grad is not supported")
+    _require_cuda(radius)
+    if radius.dim() != 1 or radius.shape[0] != rows:
+        raise ValueError(f"{what}: a per-point radius must have shape ({rows},)")
+    return 0.0, radius.detach().float().contiguous()
+
+
+def _points_ndc_args(points_ndc, first, count, idx_base):
+    if points_ndc.dim() != 2 or points_ndc.shape[1] != 3:
+        raise NotImplementedError("rasterize_points: points must be (P, 3)")
+    _require_cuda(points_ndc, first, count, idx_base)
+    p = points_ndc.detach().float().contiguous()
+    i64 = lambda t: None if t is None else t.to(torch.int64).contiguous()  # noqa: E731
+    return p, i64(first), i64(count), i64(idx_base)
+
+
+def rasterize_points_fwd(points_ndc, first, count, H, W, radius, K, idx_base=None):
+    p, first, count, idx_base = _points_ndc_args(points_ndc, first, count, idx_base)
+    r0, rpp = _radius_args(radius, p.shape[0], "rasterize_points")
+    N, dev = first.numel(), p.device
+    H, W, K = int(H), int(W), int(K)
+    idx = torch.empty((N, H, W, K), dtype=torch.int64, device=dev)
+    zbuf = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)
+    dists = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)
+    check(_lib.load().mr_rasterize_points(ptr(p), ptr(first), ptr(count), ptr(idx_base), N, p.shape[0], H, W, r0,
+                                          ptr(rpp), K, ptr(idx), ptr(zbuf), ptr(dists), _lib.stream_handle(dev)))
+    return idx, zbuf, dists
+
+
+def rasterize_points_bwd(points_ndc, first, idx, gz, gd, idx_base=None):
+    L = _lib.load()
+    p = points_ndc.detach().float().contiguous()
+    N, H, W, K = idx.shape
+    g = torch.empty_like(p)
+    gz, gd = (None if t is None else t.float().contiguous() for t in (gz, gd))
+    wsb = _ws_size(L.mr_rasterize_points_backward_workspace, p.shape[0])
+    ws = torch.empty(wsb, dtype=torch.uint8, device=p.device)
+    check(L.mr_rasterize_points_backward(ptr(p), ptr(first), ptr(idx_base), N, p.shape[0], H, W, K,
+                                         ptr(idx.contiguous()), ptr(gz), ptr(gd), ptr(g), ptr(ws), wsb,
+                                         _lib.stream_handle(p.device)))
+    return g
+
+
+class RasterizePoints(torch.autograd.Function):
+    """Drop-in for PyTorch3D's _RasterizePoints (upstream points/rasterize_points.py), naive semantics."""
+
+    @staticmethod
+    def forward(ctx, points_ndc, first, count, H, W, radius, K, idx_base=None):
+        ctx.set_materialize_grads(False)
+        idx, zbuf, dists = rasterize_points_fwd(points_ndc, first, count, H, W, radius, K, idx_base)
+        ctx.save_for_backward(points_ndc, first.to(torch.int64).contiguous(), idx,
+                              torch.empty(0) if idx_base is None else idx_base.to(torch.int64).contiguous())
+        ctx.mark_non_differentiable(idx)
+        return idx, zbuf, dists
+
+    @staticmethod
+    def backward(ctx, _gi, gz, gd):
+        p, first, idx, idx_base = ctx.saved_tensors
+        g = rasterize_points_bwd(p, first, idx, gz, gd, idx_base if idx_base.numel() else None)
+        return (g.to(p.dtype),) + (None,) * 7
+
+
+def rasterize_points(points_ndc, first, count, H, W, radius, K, idx_base=None):
+    """pytorch3d._C.rasterize_points, naive semantics (mr_rasterize_points): packed points (sum P, 3) of NDC x, NDC y
+    and view z, per-cloud ``first`` / ``count`` (N), ``radius`` in NDC units (a float, or a (sum P,) tensor), K points
+    per pixel. Returns idx (N,H,W,K) int64 (the packed index, or ``idx_base[n]`` + the index within cloud n), zbuf and
+    dists = squared NDC distance to the pixel centre, -1 where empty; differentiable w.r.t. the points."""
+    return RasterizePoints.apply(points_ndc, first, count, H, W, radius, K, idx_base)
+
+
+class ProjectPoints(torch.autograd.Function):
+    """PointsRasterizer.transform: view n projects rows src_first[n] .. + count[n] - 1 of the world points (P,3) to
+    rows dst_first[n] .. of the (total_out, 3) result (mr_project_points); views that share a cloud name the same
+    rows, and the cloud is read in place. Gradients to the points (summed over the views), R and T."""
+
+    @staticmethod
+    def forward(ctx, points, R, T, intr, src_first, dst_first, count, total_out, max_count):
+        _require_cuda(points, R, T, intr, src_first, dst_first, count)
+        p = points.detach().float().contiguous()
+        views = make_views(R.detach(), T.detach(), intr)
+        N = views.shape[0]
+        out = torch.empty((int(total_out), 3), device=p.device)
+        check(_lib.load().mr_project_points(ptr(p), ptr(src_first), ptr(dst_first), ptr(count), N, int(max_count),
+                                            ptr(views), ptr(out), _lib.stream_handle(p.device)))
+        ctx.save_for_backward(p, views, src_first, dst_first, count)
+        ctx.dtype = points.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        p, views, src_first, dst_first, count = ctx.saved_tensors
+        L = _lib.load()
+        N = views.shape[0]
+        gp = torch.empty_like(p)
+        gviews = torch.empty((N, 12), device=p.device)
+        wsb = _ws_size(L.mr_project_points_backward_workspace, p.shape[0])
+        ws = torch.empty(wsb, dtype=torch.uint8, device=p.device)
+        check(L.mr_project_points_backward(ptr(p), ptr(src_first), ptr(dst_first), ptr(count), N, p.shape[0], ptr(views),
+                                           ptr(g.float().contiguous()), ptr(gp), ptr(gviews), ptr(ws), wsb,
+                                           _lib.stream_handle(p.device)))
+        return (gp.to(ctx.dtype), gviews[:, :9].reshape(N, 3, 3), gviews[:, 9:12]) + (None,) * 6
+
+
+class CompositePoints(torch.autograd.Function):
+    """alpha_composite / norm_weighted_sum (``flags``: MR_COMPOSITE_NORM) over fragments idx / vals (N,H,W,K) and
+    features (P,C) -> (N,H,W,C) (mr_composite_points_*). With MR_COMPOSITE_DISTS ``vals`` are the rasterizer's dists
+    and alpha = 1 - dists / r^2 is formed in the kernel (``radius``: a float, or a tensor indexed by idx). The
+    feature row of a slot is idx - feat_sub[n]; ``background``: a (C,) device tensor or None. Gradients to vals and
+    the features."""
+
+    @staticmethod
+    def forward(ctx, idx, vals, feats, flags, radius, feat_sub, background):
+        _require_cuda(idx, vals, feats, feat_sub, background)
+        N, H, W, K = idx.shape
+        f = feats.detach().float().contiguous()
+        P, C = f.shape
+        ix = idx.to(torch.int64).contiguous()
+        v = vals.detach().float().contiguous()
+        if torch.is_tensor(radius):
+            r0, rpp = _radius_args(radius, radius.shape[0] if radius.dim() == 1 else -1, "compositing")
+        else:
+            r0, rpp = float(radius), None
+        out = torch.empty((N, H, W, C), device=f.device)
+        ctx.sizes = (N, H, W, K, C, P, int(flags), r0)
+        check(_lib.load().mr_composite_points_forward(ptr(ix), ptr(v), ptr(f), *ctx.sizes, ptr(rpp),
+                                                      0 if rpp is None else rpp.shape[0], ptr(feat_sub),
+                                                      ptr(background), ptr(out), _lib.stream_handle(f.device)))
+        e = lambda t: torch.empty(0) if t is None else t  # noqa: E731
+        ctx.save_for_backward(ix, v, f, e(rpp), e(feat_sub), e(background))
+        ctx.dtypes = (vals.dtype, feats.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        ix, v, f, rpp, feat_sub, background = ctx.saved_tensors
+        e = lambda t: t if t.numel() else None  # noqa: E731
+        L = _lib.load()
+        P, C = f.shape
+        gv = torch.empty_like(v)
+        gf = torch.empty_like(f)
+        wsb = _ws_size(L.mr_composite_points_backward_workspace, P, C)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=f.device)
+        check(L.mr_composite_points_backward(ptr(ix), ptr(v), ptr(f), *ctx.sizes, ptr(e(rpp)), rpp.shape[0],
+                                             ptr(e(feat_sub)), ptr(e(background)), ptr(g.float().contiguous()),
+                                             ptr(gv), ptr(gf), ptr(ws), wsb, _lib.stream_handle(f.device)))
+        return None, gv.to(ctx.dtypes[0]), gf.to(ctx.dtypes[1]), None, None, None, None

@@ -15,6 +15,9 @@ import torch
 from .cameras import PerspectiveCameras
 from .io import load_objs_as_meshes
 from .mesh_renderer import MeshRasterizer, MeshRenderer, PointLights, RasterizationSettings, SoftPhongShader
+from .points_renderer import (AlphaCompositor, NormWeightedCompositor, PointFragments,  # noqa: F401
+                              PointsRasterizationSettings, PointsRasterizer, PointsRenderer, alpha_composite,
+                              norm_weighted_sum)
 
 # renderer.py:46-58
 _K = [[914.4831543, 0.0, 645.47546387, 0.0],

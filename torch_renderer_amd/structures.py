@@ -422,6 +422,22 @@ class Pointclouds:
         pc._num = self._num if self._num is not None and self._num.device == new_points_padded.device else None
         return pc
 
+    def extend(self, N: int):
+        """upstream Pointclouds.extend: every cloud N times over, as references to the same tensors. A batch of one
+        cloud extended is what the point rasterizer takes as one cloud shared by N views (is_shared())."""
+        if not isinstance(N, int):
+            raise ValueError("N must be an integer.")
+        if N <= 0:
+            raise ValueError("N must be > 0.")
+        pc = Pointclouds([p for p in self.points_list() for _ in range(N)])
+        if len(self) == 1:
+            pc._shared = self.points_list()[0]
+        return pc
+
+    def is_shared(self):
+        """Whether every cloud of the batch is the same tensor (built by extend() from a batch of one)."""
+        return getattr(self, "_shared", None) is not None
+
     def _map(self, fn):
         pc = Pointclouds.__new__(Pointclouds)
         pc._counts = list(self._counts)

@@ -9,8 +9,10 @@ reference's DepthRender with return_silhouette=True rasterizes twice
 pass. ``DepthColorRender`` adds the benchmark's frame: depth + silhouette +
 RGB from one raster pass.
 
-Out of scope: the point renderers (torch_renderer.py:162-230),
-which cannot run in the reference (undefined ``Ts``/``device``).
+``AlphaPointRender`` / ``NormPointRender`` (torch_renderer.py:162-207) run on the point
+rasterizer and compositors of ``points_renderer``; they do what the reference evidently
+meant (its ``render`` passes an undefined ``Ts``). ``PulsarPointRender`` (:209-230) is out
+of scope and raises.
 """
 from __future__ import annotations
 
@@ -295,3 +297,58 @@ class DepthColorRender(DifferentiableRenderer):
         cfg = ShadeConfig(H=self._image_size[0], W=self._image_size[1], light_location=self._light_location)
         out = render_mesh_batch(meshes, self._cameras, self._image_size, R, tvec, cfg, pose_cv=True)
         return out["depth"], out["sil"], out["rgb"]
+
+
+class _PointRender(DifferentiableRenderer):
+    """torch_renderer.py:163-207: PointsRenderer over PointsRasterizationSettings(radius, points_per_pixel) with the
+    subclass's compositor. ``render(points, R, tvec, features)`` takes OpenCV poses as DepthRender does and returns
+    images[..., :3]; the features come with the call (Pointclouds here holds none)."""
+    _compositor = None
+
+    def __init__(self, K, image_size, radius=0.003, points_per_pixel=10, background_color=(0, 0, 0), device="cuda:0"):
+        super().__init__(K, image_size, device=device)
+        print(f"INFO: Initializing {type(self).__name__} ...")
+        from .points_renderer import PointsRasterizationSettings, PointsRasterizer, PointsRenderer
+
+        raster_settings = PointsRasterizationSettings(image_size=self._image_size, radius=radius,
+                                                      points_per_pixel=points_per_pixel)
+        self._renderer = PointsRenderer(rasterizer=PointsRasterizer(cameras=self._cameras,
+                                                                    raster_settings=raster_settings),
+                                        compositor=self._compositor(background_color=background_color))
+
+    def render(self, points, R, tvec, features=None):
+        from .structures import Pointclouds
+
+        assert isinstance(points, Pointclouds), \
+            "[Error] PointRender.render, points must be pytorch3d.structures.Pointclouds"
+        Rs, ts = self._camera_pose_from_opencv_to_pytorch(R, tvec)
+        return self._renderer(points, features=features, R=Rs, T=ts)[..., :3]
+
+
+def _alpha_compositor(**kw):
+    from .points_renderer import AlphaCompositor
+
+    return AlphaCompositor(**kw)
+
+
+def _norm_compositor(**kw):
+    from .points_renderer import NormWeightedCompositor
+
+    return NormWeightedCompositor(**kw)
+
+
+class AlphaPointRender(_PointRender):
+    """torch_renderer.py:163-184 (AlphaCompositor)."""
+    _compositor = staticmethod(_alpha_compositor)
+
+
+class NormPointRender(_PointRender):
+    """torch_renderer.py:186-207 (NormWeightedCompositor)."""
+    _compositor = staticmethod(_norm_compositor)
+
+
+class PulsarPointRender(DifferentiableRenderer):
+    """torch_renderer.py:209-230: the Pulsar sphere renderer is not built."""
+
+    def __init__(self, K, image_size, radius=0.003, points_per_pixel=10, device="cuda:0"):
+        raise NotImplementedError("PulsarPointRender: the Pulsar renderer is not implemented on the MI355X path")
