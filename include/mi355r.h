@@ -525,6 +525,62 @@ int32_t mr_posed_chamfer(const float* x, const float* y, int64_t P1, int64_t P2,
                          int32_t norm, int32_t flags, float* out, int32_t* idx_x, int32_t* idx_y, float* pose_grad,
                          void* ws, size_t ws_bytes, void* stream);
 
+/* Point-to-triangle distances (PyTorch3D point_mesh_face_distance, point_face_distance, face_point_distance) of a
+ * packed batch of N meshes and N clouds that pair up one to one: points (P,3) and verts (V,3) float32, faces (T,3)
+ * int32 over packed vertex ids; points_first / points_count and faces_first / faces_count (N) int64 device arrays
+ * give cloud n's points and mesh n's faces as a range of the packed arrays (a range that does not lie inside its
+ * array counts as empty; a face with a vertex id outside [0, V) is skipped). max_points / max_faces: host-side
+ * upper bounds of the counts, which size the grids (P and T always serve); the host reads nothing from the device.
+ *
+ * d(p, tri) for tri = (v0, v1, v2) is the squared distance from p to the closest point of the triangle, float32 in
+ * a fixed operation order without FMA, with IEEE division and square root. With n = (v1 - v0) x (v2 - v0) and
+ * area = |n| / 2: if area >= min_triangle_area, |n| > 1e-8 and the barycentric coordinates of p's orthogonal
+ * projection onto the plane all lie in [0, 1], d = ((v0 - p) . n / |n|)^2. Otherwise d = min(seg(p, v0, v1),
+ * seg(p, v1, v2), seg(p, v2, v0)), where seg(p, a, b) = |p - (a + t (b - a))|^2 with t = clamp((p - a) . (b - a) /
+ * |b - a|^2, 0, 1), and = |p - b|^2 when |b - a|^2 <= 1e-8. So a triangle below the area threshold is its three
+ * edges and a collapsed one a point; finite coordinates never give NaN or Inf (short of float32 overflow).
+ * min_triangle_area = 0 gives the true point-to-triangle distance. Equal distances resolve to the lowest index,
+ * in both directions.
+ *
+ * mr_point_face_nearest writes for every point its nearest face of its own mesh (dist_p (P), idx_p (P): the face's
+ * index within the mesh) and for every face its nearest point of its own cloud (dist_f (T), idx_f (T): the point's
+ * index within the cloud); each output may be NULL. A point whose mesh has no faces and a face whose cloud is
+ * empty get 0 / -1. Elements outside every range are not written.
+ *
+ * mr_point_mesh_face_forward: out[0] = (1/N) sum_n ((1/P_n) sum_p dist_p + (1/T_n) sum_t dist_f); a pair whose
+ * cloud or mesh is empty contributes 0. Sums are float64 in a fixed order. idx_p / idx_f (may be NULL) and coef
+ * (2,N; may be NULL) are what the backward reads.
+ *
+ * mr_point_mesh_face_backward writes grad_points (P,3) and grad_verts (V,3): for every winning pair, with c the
+ * closest point and b its barycentrics (those of the projection in the plane case; (1 - t, t) on the winning edge
+ * and 0 at the third vertex otherwise), dd/dp = 2 (p - c) and dd/dv_i = -2 b_i (p - c), times the pair's weight:
+ * coef[direction, n] * grad_out[0] (grad_out: 1 float on the device), or grad_dist_p[point] / grad_dist_f[face]
+ * where those per-distance upstream gradients are given (the unreduced functions; coef and grad_out may then be
+ * NULL). A NULL idx_p / idx_f leaves that direction out. Everything many-to-one is summed with 64-bit fixed-point
+ * integer atomics, so the result is bitwise reproducible. min_triangle_area must be the forward's. The *_workspace
+ * queries return 0 when a size is out of range. */
+size_t mr_point_face_nearest_workspace(int64_t N, int64_t P, int64_t T);
+int32_t mr_point_face_nearest(const float* points, int64_t P, const int64_t* points_first, const int64_t* points_count,
+                              int64_t max_points, const float* verts, int64_t V, const int32_t* faces, int64_t T,
+                              const int64_t* faces_first, const int64_t* faces_count, int64_t max_faces, int64_t N,
+                              float min_triangle_area, float* dist_p, int32_t* idx_p, float* dist_f, int32_t* idx_f,
+                              void* ws, size_t ws_bytes, void* stream);
+size_t mr_point_mesh_face_workspace(int64_t N, int64_t P, int64_t T);
+int32_t mr_point_mesh_face_forward(const float* points, int64_t P, const int64_t* points_first,
+                                   const int64_t* points_count, int64_t max_points, const float* verts, int64_t V,
+                                   const int32_t* faces, int64_t T, const int64_t* faces_first,
+                                   const int64_t* faces_count, int64_t max_faces, int64_t N, float min_triangle_area,
+                                   int32_t* idx_p, int32_t* idx_f, float* coef, float* out, void* ws, size_t ws_bytes,
+                                   void* stream);
+size_t mr_point_mesh_face_backward_workspace(int64_t P, int64_t V);
+int32_t mr_point_mesh_face_backward(const float* points, int64_t P, const int64_t* points_first,
+                                    const int64_t* points_count, int64_t max_points, const float* verts, int64_t V,
+                                    const int32_t* faces, int64_t T, const int64_t* faces_first,
+                                    const int64_t* faces_count, int64_t max_faces, int64_t N, float min_triangle_area,
+                                    const int32_t* idx_p, const int32_t* idx_f, const float* coef, const float* grad_out,
+                                    const float* grad_dist_p, const float* grad_dist_f, float* grad_points,
+                                    float* grad_verts, void* ws, size_t ws_bytes, void* stream);
+
 /* Point-cloud rendering (PyTorch3D rasterize_points with naive semantics, alpha_composite, norm_weighted_sum).
  *
  * mr_rasterize_points: points (total_points,3) hold NDC x, NDC y and view z; view n draws rows first[n] ..

@@ -85,6 +85,8 @@ _VP = ctypes.c_void_p
 _I64 = ctypes.c_int64
 _I32 = ctypes.c_int32
 _SZ = ctypes.c_size_t
+# mr_point_face_nearest / mr_point_mesh_face_*: the packed batch (points .. max_points, verts .. max_faces, N, min area)
+_PM_BATCH = [_VP, _I64, _VP, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _I64, _I64, ctypes.c_float]
 _SIGS = [
     ("mr_last_error", ctypes.c_char_p, []),
     ("mr_version", _I32, []),
@@ -160,6 +162,12 @@ _SIGS = [
     ("mr_chamfer_backward_workspace", _SZ, [_I64, _I64, _I64]),
     ("mr_chamfer_backward", _I32, [_VP, _VP, _I64, _I64, _I64, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ,
                                    _VP]),
+    ("mr_point_face_nearest_workspace", _SZ, [_I64, _I64, _I64]),
+    ("mr_point_face_nearest", _I32, [*_PM_BATCH, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    ("mr_point_mesh_face_workspace", _SZ, [_I64, _I64, _I64]),
+    ("mr_point_mesh_face_forward", _I32, [*_PM_BATCH, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    ("mr_point_mesh_face_backward_workspace", _SZ, [_I64, _I64]),
+    ("mr_point_mesh_face_backward", _I32, [*_PM_BATCH, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     ("mr_posed_chamfer_workspace", _SZ, [_I64, _I64, _I64]),
     ("mr_posed_chamfer", _I32, [_VP, _VP, _I64, _I64, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     ("mr_icp_workspace", _SZ, [_I64, _I64, _I64]),

@@ -417,6 +417,199 @@ class PosedChamfer(torch.autograd.Function):
         return None, None, gR, gT, gs, None, None
 
 
+# --------------------------------------------------------------------------- point to mesh (csrc/mr_pointmesh.hip)
+@dataclass
+class PointMeshBatch:
+    """How N clouds and N meshes lie in the packed arrays the point-to-face kernels read: ``points_first`` /
+    ``points_count`` and ``faces_first`` / ``faces_count`` (N) int64 device tensors, ``faces`` (T,3) int32 over packed
+    vertex ids, and the host-side bounds ``max_points`` / ``max_faces`` of the counts that size the grids."""
+    points_first: torch.Tensor
+    points_count: torch.Tensor
+    max_points: int
+    faces: torch.Tensor
+    faces_first: torch.Tensor
+    faces_count: torch.Tensor
+    max_faces: int
+
+    @property
+    def N(self):
+        return int(self.points_first.shape[0])
+
+
+_FACE_TABLE_CACHE: dict = {}
+
+
+def mesh_face_table(faces_list, Vs):
+    """(faces (T,3) int32 over packed vertex ids, faces_first (N), faces_count (N) int64, max_faces) of the meshes
+    (faces_list[m] (F_m,3) over Vs[m] vertices), built once per faces tensors and cached like mesh_prior_topology: on
+    the identity and version of each tensor, so a steady loop or a captured HIP graph uploads nothing here."""
+    faces_list = list(faces_list)
+    Vs = tuple(int(v) for v in Vs)
+    key = tuple(id(f) for f in faces_list) + Vs
+    hit = _FACE_TABLE_CACHE.get(key)
+    if hit is not None and all(r() is f and ver == f._version for r, ver, f in zip(hit[0], hit[1], faces_list)):
+        return hit[2]
+    dev = faces_list[0].device
+    counts = [int(f.shape[0]) for f in faces_list]
+    voff = np.cumsum((0,) + Vs[:-1])
+    packed = torch.cat([f.reshape(-1, 3).to(torch.int32) + int(o) for f, o in zip(faces_list, voff)], 0).contiguous()
+    first = torch.tensor(np.cumsum([0] + counts[:-1]), dtype=torch.int64).to(dev)
+    table = (packed, first, torch.tensor(counts, dtype=torch.int64).to(dev), max(counts))
+    if len(_FACE_TABLE_CACHE) > 64:
+        _FACE_TABLE_CACHE.clear()
+    _FACE_TABLE_CACHE[key] = ([weakref.ref(f) for f in faces_list], [f._version for f in faces_list], table)
+    return table
+
+
+def _pm_args(points, verts, batch, min_triangle_area):
+    """The checked inputs of a point-to-face call: contiguous float32 points and verts, and the C ABI's leading
+    arguments (the packed batch)."""
+    if points.dim() != 2 or verts.dim() != 2 or batch.faces.dim() != 2 or batch.faces.shape[1] != 3:
+        raise ValueError("point-face distance: points (P, D), verts (V, D) and faces (T, 3) are packed 2-D tensors")
+    if points.shape[1] != 3 or verts.shape[1] != 3:
+        raise NotImplementedError("point-face distance: only D = 3 is built")
+    N = batch.N
+    for t in (batch.points_count, batch.faces_first, batch.faces_count):
+        if tuple(t.shape) != (N,):
+            raise ValueError("point-face distance: the first / count tensors must all be of shape (N,)")
+    if N < 1:
+        raise ValueError("point-face distance: N must be >= 1")
+    if not float(min_triangle_area) >= 0.0:
+        raise ValueError("point-face distance: min_triangle_area must be >= 0")
+    _require_cuda(points, verts, batch.faces, batch.points_first, batch.points_count, batch.faces_first,
+                  batch.faces_count)
+    pf, vf = points.detach().float().contiguous(), verts.detach().float().contiguous()
+    i64 = [t.detach().to(torch.int64).contiguous() for t in (batch.points_first, batch.points_count, batch.faces_first,
+                                                             batch.faces_count)]
+    faces = batch.faces.detach().to(torch.int32).contiguous()
+    P, V, T = pf.shape[0], vf.shape[0], faces.shape[0]
+    args = (ptr(pf), P, ptr(i64[0]), ptr(i64[1]), int(batch.max_points), ptr(vf), V, ptr(faces), T, ptr(i64[2]),
+            ptr(i64[3]), int(batch.max_faces), N, float(min_triangle_area))
+    return pf, vf, args, (pf, vf, faces, *i64)
+
+
+def _pm_nearest(points, verts, batch, min_triangle_area, want=(True, True, True, True)):
+    pf, vf, args, keep = _pm_args(points, verts, batch, min_triangle_area)
+    L = _lib.load()
+    dev = pf.device
+    P, T = pf.shape[0], batch.faces.shape[0]
+    outs = [torch.empty(n, dtype=dt, device=dev) if w else None
+            for n, dt, w in zip((P, P, T, T), (torch.float32, torch.int32, torch.float32, torch.int32), want)]
+    wsb = _ws_size(L.mr_point_face_nearest_workspace, batch.N, P, T)
+    if wsb == 0:
+        raise NotImplementedError("mi355r: point-face nearest: more than 65535 meshes or a batch too large for "
+                                  "32-bit indices")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    check(L.mr_point_face_nearest(*args, ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), ptr(outs[3]), ptr(ws), wsb,
+                                  _lib.stream_handle(dev)))
+    return outs, keep
+
+
+def point_face_nearest(points, points_first, points_count, verts, faces, faces_first, faces_count,
+                       min_triangle_area=5e-3, max_points=None, max_faces=None):
+    """(dist_p, idx_p, dist_f, idx_f) of a packed batch of N clouds and N meshes that pair up one to one: for every
+    point of ``points`` (P,3) the squared distance to and the index (within its mesh) of the nearest face of its own
+    mesh (float32 / int32 (P,)), and for every face of ``faces`` (T,3) over ``verts`` (V,3) the nearest point of its
+    own cloud ((T,), index within the cloud). ``*_first`` / ``*_count`` (N) give each cloud's and mesh's range of the
+    packed arrays; ``max_points`` / ``max_faces`` are host-side bounds of the counts (default: P and T). The
+    distance is the one include/mi355r.h states (a face below ``min_triangle_area`` is its three edges), float32 in
+    a fixed operation order; equal distances take the lowest index; a point or face without a counterpart gets
+    0 / -1. No autograd; one memset and two launches (mr_point_face_nearest), nothing synchronises."""
+    batch = PointMeshBatch(points_first, points_count, points.shape[0] if max_points is None else max_points, faces,
+                           faces_first, faces_count, faces.shape[0] if max_faces is None else max_faces)
+    outs, _ = _pm_nearest(points, verts, batch, min_triangle_area)
+    return tuple(outs)
+
+
+def _pm_backward(keep, batch_args, idx_p, idx_f, coef, g, gdp, gdf):
+    pf, vf = keep[0], keep[1]
+    L = _lib.load()
+    gp, gv = torch.empty_like(pf), torch.empty_like(vf)
+    wsb = _ws_size(L.mr_point_mesh_face_backward_workspace, pf.shape[0], vf.shape[0])
+    ws = torch.empty(wsb, dtype=torch.uint8, device=pf.device)
+    check(L.mr_point_mesh_face_backward(*batch_args, ptr(idx_p), ptr(idx_f), ptr(coef), ptr(g), ptr(gdp), ptr(gdf),
+                                        ptr(gp), ptr(gv), ptr(ws), wsb, _lib.stream_handle(pf.device)))
+    return gp, gv
+
+
+class PointMeshFaceDistance(torch.autograd.Function):
+    """The point-to-mesh face loss of packed ``points`` (P,3) and ``verts`` (V,3) over a PointMeshBatch: one memset
+    and three launches forward (both directions' nearest primitives, per-element reduce, final;
+    mr_point_mesh_face_forward), one memset and two launches backward (mr_point_mesh_face_backward). Returns a 0-dim
+    tensor, differentiable w.r.t. points and verts; bitwise reproducible."""
+
+    @staticmethod
+    def forward(ctx, points, verts, batch, min_triangle_area):
+        pf, vf, args, keep = _pm_args(points, verts, batch, min_triangle_area)
+        L = _lib.load()
+        dev = pf.device
+        N, P, T = batch.N, pf.shape[0], batch.faces.shape[0]
+        want = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        out = torch.empty(1, device=dev)
+        ip = torch.empty(P, dtype=torch.int32, device=dev) if want else None
+        it = torch.empty(T, dtype=torch.int32, device=dev) if want else None
+        coef = torch.empty((2, N), device=dev) if want else None
+        wsb = _ws_size(L.mr_point_mesh_face_workspace, N, P, T)
+        if wsb == 0:
+            raise NotImplementedError("mi355r: point-mesh face distance: more than 65535 meshes or a batch too large "
+                                      "for 32-bit indices")
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        check(L.mr_point_mesh_face_forward(*args, ptr(ip), ptr(it), ptr(coef), ptr(out), ptr(ws), wsb,
+                                           _lib.stream_handle(dev)))
+        ctx.set_materialize_grads(False)
+        if want:
+            ctx.save_for_backward(*keep, ip, it, coef)
+            ctx.args = (args[4], args[11], N, args[13], points.dtype, verts.dtype)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None
+        pf, vf, faces, p1, pc, f1, fc, ip, it, coef = ctx.saved_tensors
+        maxp, maxf, N, area, pdt, vdt = ctx.args
+        g = g.detach().float().reshape(1).contiguous()
+        _require_cuda(g)
+        args = (ptr(pf), pf.shape[0], ptr(p1), ptr(pc), maxp, ptr(vf), vf.shape[0], ptr(faces), faces.shape[0], ptr(f1),
+                ptr(fc), maxf, N, area)
+        gp, gv = _pm_backward((pf, vf), args, ip, it, coef, g, None, None)
+        return gp.to(pdt), gv.to(vdt), None, None
+
+
+class PointFaceDistances(torch.autograd.Function):
+    """The unreduced distances of one direction over the same kernels: ``direction`` 0 every point's squared distance
+    to its nearest face (P,), 1 every face's to its nearest point (T,). The backward takes the per-distance upstream
+    gradient (mr_point_mesh_face_backward's grad_dist_p / grad_dist_f)."""
+
+    @staticmethod
+    def forward(ctx, points, verts, batch, min_triangle_area, direction):
+        want = (direction == 0, direction == 0, direction == 1, direction == 1)
+        outs, keep = _pm_nearest(points, verts, batch, min_triangle_area, want)
+        ctx.set_materialize_grads(False)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            ctx.save_for_backward(*keep, outs[1 + 2 * direction])
+            ctx.args = (int(batch.max_points), int(batch.max_faces), batch.N, float(min_triangle_area), direction,
+                        points.dtype, verts.dtype)
+        ctx.mark_non_differentiable(outs[1 + 2 * direction])
+        return outs[2 * direction], outs[1 + 2 * direction]
+
+    @staticmethod
+    def backward(ctx, g, _gi):
+        if g is None:
+            return None, None, None, None, None
+        pf, vf, faces, p1, pc, f1, fc, idx = ctx.saved_tensors
+        maxp, maxf, N, area, direction, pdt, vdt = ctx.args
+        g = g.detach().float().contiguous()
+        _require_cuda(g)
+        args = (ptr(pf), pf.shape[0], ptr(p1), ptr(pc), maxp, ptr(vf), vf.shape[0], ptr(faces), faces.shape[0], ptr(f1),
+                ptr(fc), maxf, N, area)
+        if direction == 0:
+            gp, gv = _pm_backward((pf, vf), args, idx, None, None, None, g, None)
+        else:
+            gp, gv = _pm_backward((pf, vf), args, None, idx, None, None, None, g)
+        return gp.to(pdt), gv.to(vdt), None, None, None
+
+
 # Iterations enqueued between two reads of the device status: a read costs ~14 us, an iteration enqueued after
 # convergence ~18 us (tools/icp_bench.py, DESIGN.md §3, ICP)
 ICP_STATUS_BATCH = 8

@@ -8,6 +8,12 @@ never writes the (N, P1, P2) distance matrix (kernels.ChamferDistance, csrc/mr_p
 105-126 and pytorch3d_icp_evaluation.py:158-239) in one fused pass that never materialises the S transformed clouds,
 with gradients to the poses (kernels.PosedChamfer).
 
+Point to mesh (``pytorch3d.loss.point_mesh_face_distance`` for a target that is a scan, deform_mesh_from_pcd.py):
+``point_mesh_face_distance`` is one autograd node over an all-pairs point-to-triangle kernel that never writes a
+(P, T) matrix (kernels.PointMeshFaceDistance, csrc/mr_pointmesh.hip); ``point_face_distance`` and
+``face_point_distance`` are upstream's unreduced per-point and per-face distances over the same kernels.
+Deterministic.
+
 Mesh shape priors (``pytorch3d.loss.mesh_edge_loss`` / ``mesh_laplacian_smoothing`` / ``mesh_normal_consistency``,
 called together by update_mesh_shape_prior_losses at deform_mesh_with_color.py:248-256 and mesh_deformer.py:
 314-320): ``mesh_shape_priors`` returns all three from one autograd node — one HIP pass over the edges,
@@ -40,8 +46,9 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .kernels import ChamferDistance, MeshShapePriors, PosedChamfer, _require_cuda, mesh_prior_topology
-from .structures import Pointclouds
+from .kernels import (ChamferDistance, MeshShapePriors, PointFaceDistances, PointMeshBatch, PointMeshFaceDistance,
+                      PosedChamfer, _require_cuda, mesh_prior_topology)
+from .structures import Meshes, Pointclouds
 
 
 def _rgba_base(t: torch.Tensor, channels):
@@ -220,3 +227,69 @@ def posed_chamfer_distance(x, y, R, T=None, s=None, *, norm: int = 2, point_redu
     flags = (_lib.MR_CHAMFER_POINT_MEAN if point_reduction == "mean" else 0) | \
         (_lib.MR_CHAMFER_SINGLE if single_directional else 0)
     return PosedChamfer.apply(x, y, R, T, s, flags, norm)
+
+
+def point_mesh_face_distance(meshes, pcls, min_triangle_area: float = 5e-3):
+    """pytorch3d.loss.point_mesh_face_distance for a ``Meshes`` and a ``Pointclouds`` of equal batch size: per pair the
+    mean over the cloud's points of the squared distance to the nearest face of its mesh, plus the mean over the
+    mesh's faces of the squared distance to the nearest point of its cloud; then the mean over the batch. A pair
+    whose cloud is empty or whose mesh has no faces contributes 0 and receives no gradient.
+
+    The distance is upstream's: a face whose area is below ``min_triangle_area`` (default 5e-3, upstream's) counts as
+    its three edges, not as a filled triangle; ``min_triangle_area=0`` gives the true point-to-triangle distance.
+    Differentiable w.r.t. the points and the vertices (through ``offset_verts`` to a ``deform_verts`` leaf; the
+    shared tensors of an ``extend``-ed batch receive the sum over their copies); bitwise reproducible; nothing
+    synchronises."""
+    if not isinstance(meshes, Meshes) or not isinstance(pcls, Pointclouds):
+        raise ValueError("point_mesh_face_distance: the inputs are a Meshes and a Pointclouds")
+    if len(meshes) != len(pcls):
+        raise ValueError("meshes and pointclouds must be equal sized batches")
+    if len(meshes) < 1:
+        raise ValueError("point_mesh_face_distance: the batch is empty")
+    points = pcls.points_packed()
+    verts = meshes.verts_packed()
+    if points.dim() != 2 or points.shape[1] != 3 or verts.shape[1] != 3:
+        raise NotImplementedError("point_mesh_face_distance: only D = 3 is built")
+    faces, faces_first, faces_count, max_faces = meshes._face_table()
+    batch = PointMeshBatch(pcls.cloud_to_packed_first_idx(), pcls.num_points_per_cloud(), max(pcls.counts()), faces,
+                           faces_first, faces_count, max_faces)
+    return PointMeshFaceDistance.apply(points, verts, batch, float(min_triangle_area))
+
+
+def _tris_batch(points, points_first_idx, tris, tris_first_idx, max_points, max_tris):
+    """The PointMeshBatch of upstream's (points, points_first_idx, tris (T,3,3), tris_first_idx) arguments: the
+    triangles' corners are the vertices, under a trivial face table; the counts follow from the first indices on the
+    device."""
+    if points.dim() != 2 or tris.dim() != 3 or tuple(tris.shape[1:]) != (3, points.shape[1]):
+        raise ValueError("points must be (P, D) and tris (T, 3, D)")
+    if points.shape[1] != 3:
+        raise NotImplementedError("point-face distance: only D = 3 is built")
+    if points_first_idx.dim() != 1 or points_first_idx.shape != tris_first_idx.shape:
+        raise ValueError("points_first_idx and tris_first_idx must be (N,) tensors of one batch size")
+    _require_cuda(points, tris, points_first_idx, tris_first_idx)
+    P, T = points.shape[0], tris.shape[0]
+
+    def count(first, total):
+        first = first.to(torch.int64)
+        return first, torch.cat((first[1:], first.new_full((1,), total))) - first
+
+    pf, pc = count(points_first_idx, P)
+    ff, fc = count(tris_first_idx, T)
+    faces = torch.arange(3 * T, dtype=torch.int32, device=tris.device).view(T, 3)
+    return PointMeshBatch(pf, pc, P if max_points is None else min(int(max_points), P), faces, ff, fc,
+                          T if max_tris is None else min(int(max_tris), T))
+
+
+def point_face_distance(points, points_first_idx, tris, tris_first_idx, max_points=None, min_triangle_area: float = 5e-3):
+    """upstream's unreduced point_face_distance: (P,) squared distances from every point of the packed ``points`` (P,3)
+    to the nearest of its own mesh's triangles ``tris`` (T,3,3); ``*_first_idx`` (N,) are the packed first indices,
+    ``max_points`` a bound of the points per cloud. Differentiable w.r.t. points and tris."""
+    batch = _tris_batch(points, points_first_idx, tris, tris_first_idx, max_points, None)
+    return PointFaceDistances.apply(points, tris.reshape(-1, 3), batch, float(min_triangle_area), 0)[0]
+
+
+def face_point_distance(points, points_first_idx, tris, tris_first_idx, max_tris=None, min_triangle_area: float = 5e-3):
+    """upstream's unreduced face_point_distance: (T,) squared distances from every triangle of ``tris`` (T,3,3) to the
+    nearest point of its own cloud. Differentiable w.r.t. points and tris."""
+    batch = _tris_batch(points, points_first_idx, tris, tris_first_idx, None, max_tris)
+    return PointFaceDistances.apply(points, tris.reshape(-1, 3), batch, float(min_triangle_area), 1)[0]

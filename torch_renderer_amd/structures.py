@@ -233,6 +233,21 @@ class Meshes:
         counts = self.num_faces_per_mesh()
         return torch.cumsum(counts, 0) - counts
 
+    def faces_packed_to_mesh_idx(self):
+        """(sum F,) int64: the mesh every packed face belongs to."""
+        counts = [f.shape[0] for f in self.faces_list()]  # host side: the output size is known, nothing synchronises
+        return torch.repeat_interleave(torch.arange(len(self), device=self.device),
+                                       torch.tensor(counts, device=self.device), output_size=sum(counts))
+
+    def _face_table(self):
+        """(packed int32 faces, first, count, max count) for the point-to-face kernels, cached on the faces tensors
+        (kernels.mesh_face_table): an offset_verts result keeps its source's tensors, so a loop uploads nothing."""
+        from .kernels import mesh_face_table
+
+        if self._shared is not None:
+            return mesh_face_table([self._faces_list[0]] * self._shared, [self._verts_list[0].shape[0]] * self._shared)
+        return mesh_face_table(self._faces_list, [v.shape[0] for v in self._verts_list])
+
     def _prior_topology(self):
         from .kernels import mesh_prior_topology
 
@@ -391,6 +406,20 @@ class Pointclouds:
         if self._num is None:
             self._num = torch.tensor(self._counts, dtype=torch.int64, device=self.device)
         return self._num
+
+    def cloud_to_packed_first_idx(self):
+        """(N,) int64: the index of every cloud's first point in points_packed(). Built from the host-side counts once."""
+        if getattr(self, "_first", None) is None or self._first.device != self.device:
+            first = [0]
+            for c in self._counts[:-1]:
+                first.append(first[-1] + c)
+            self._first = torch.tensor(first[:len(self._counts)], dtype=torch.int64).to(self.device)
+        return self._first
+
+    def packed_to_cloud_idx(self):
+        """(sum P,) int64: the cloud every packed point belongs to."""
+        return torch.repeat_interleave(torch.arange(len(self), device=self.device), self.num_points_per_cloud(),
+                                       output_size=sum(self._counts))
 
     def points_list(self):
         if self._list is None:
