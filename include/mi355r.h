@@ -654,6 +654,33 @@ int32_t mr_workspace_stats(const void* workspace, int64_t N, int64_t total_faces
 int32_t mr_workspace_counters(const void* workspace, int64_t N, int64_t total_faces, int32_t H, int32_t W,
                               int32_t max_faces_per_bin, int32_t* out8, void* stream);
 
+/* K nearest neighbours (PyTorch3D knn_points, 1 <= K <= 32; MR_EUNSUPPORTED above). For every point of p1 (N,P1,3)
+ * the K smallest (distance, index) pairs over p2[n, :lengths2[n]], ascending, with the distance of the chamfer calls
+ * above: equal distances resolve to the lower index, inside the K kept and at the K-th / (K+1)-th boundary. dists
+ * (N,P1,K) float32, idx (N,P1,K) int32; slots k >= min(K, lengths2[n]) and rows i >= lengths1[n] are 0 / -1.
+ * One launch whose workgroups each own a tile of queries and scan every target of their cloud, the K-deep lists in
+ * registers; only when N * query tiles < 256 is the target range cut into <= 16 splits (chosen from the shapes
+ * alone), whose sorted partial lists go through the workspace (8 K splits bytes per query) to a merging launch. The
+ * result does not depend on the splits. No memset, no atomics; bitwise reproducible. mr_knn_geometry (host only)
+ * returns what the launch would use: queries per workgroup, splits, and the targets staged in LDS at a time (each
+ * pointer may be NULL).
+ *
+ * mr_knn_points_backward: for grad_dists (N,P1,K), grad_p1[n,i] = sum_k 2 g (p1[n,i] - p2[n,idx]) and grad_p2[n,j] =
+ * -(the sum of those addends over the (i,k) with idx = j); norm 1: g sign(.) for 2 g (.). Slots with idx < 0 add
+ * nothing and their g is not read. One memset and two launches; the many-to-one part is summed with 64-bit
+ * fixed-point integer atomics (bitwise reproducible; addends of magnitude >= 2^24 take float atomics). */
+size_t mr_knn_points_workspace(int64_t N, int64_t P1, int64_t P2, int32_t K);
+int32_t mr_knn_points(const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2, const int64_t* lengths1,
+                      const int64_t* lengths2, int32_t norm, int32_t K, float* dists, int32_t* idx, void* ws,
+                      size_t ws_bytes, void* stream);
+size_t mr_knn_points_backward_workspace(int64_t N, int64_t P1, int64_t P2, int32_t K);
+int32_t mr_knn_points_backward(const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2,
+                               const int64_t* lengths1, const int64_t* lengths2, int32_t norm, int32_t K,
+                               const int32_t* idx, const float* grad_dists, float* grad_p1, float* grad_p2, void* ws,
+                               size_t ws_bytes, void* stream);
+int32_t mr_knn_geometry(int64_t N, int64_t P1, int64_t P2, int32_t K, int32_t* queries_per_group, int32_t* splits,
+                        int32_t* lds_chunk);
+
 /* Per-kernel timing with HIP events recorded on each launch's stream (bench.py).
  * enable=1 clears and starts collection; mr_timing_read synchronizes on the
  * recorded events and returns, per kernel id, launches and summed ms. */

@@ -1,0 +1,334 @@
+// mi355r — K nearest neighbours of point clouds (PyTorch3D knn_points, 1 <= K <= 32) and the gradient of their
+// distances: mr_knn_points / mr_knn_points_backward / mr_knn_geometry of include/mi355r.h.
+//
+//   k_knn         a workgroup of 128 threads owns a tile of queries (Q per thread, in registers) and scans a range of
+//                 its cloud's targets itself, in ascending LDS chunks of <= 1024 float4 read as a broadcast (k_posed_nn's
+//                 shape). Every query keeps its KB smallest keys, (float bits of dist) << 32 | target index, ascending
+//                 in registers: KB is the compile-time bucket (1, 2, 4, 8, 16, 32) the requested K rounds up to, and Q
+//                 = 4, 4, 4, 4, 2, 1 keeps the lists at <= 64 VGPRs. A candidate costs one compare, its distance bits
+//                 against the high word of the worst kept key (targets arrive in ascending index order, so an equal
+//                 distance never displaces a kept key: ties go to the lowest index); only a smaller one runs the
+//                 unrolled insertion. With splits == 1 the range is the whole cloud and the workgroup writes dists / idx
+//                 itself: no key buffer, memset, atomic or merge. Only when N * query tiles < 256 (the CUs) is the
+//                 target range cut into <= 16 splits, from the shapes alone; a workgroup then writes its K sorted keys
+//                 per query into the workspace (8 K splits bytes per query) and
+//   k_knn_merge   (one thread per query) merges a query's partial lists by key with the same insertion and decodes.
+//                 The key order is total, so the K kept do not depend on the splits or the chunk size.
+//   k_knn_bwd     one thread per query: grad_p1 = sum_k 2 g (p1 - p2[idx]) (norm 1: g sign(.)) with a plain store, and
+//                 the same addends into the targets' rows with 64-bit fixed-point integer atomics (mr_common.h);
+//   k_knn_bwd_p2  grad_p2 = -(row). Slots with idx < 0 contribute nothing and their g is not read.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/mi355r.h"
+#include "mr_common.h"
+#include "mr_host.h"
+#include "mr_cloud.h"
+
+#define MRK_BLOCK 128          // threads of a k_knn workgroup (two waves)
+#define MRK_MAXCHUNK 1024      // targets staged at a time (16 KiB of LDS)
+#define MRK_MAXK 32
+#define MRK_MAXSPLIT 16
+#define MRK_CUS 256            // fewer (cloud, query tile) pairs than this: the target range is split
+#define MRK_WANT_GROUPS 1024   // workgroups a split launch aims for
+#define MRK_SPLIT_ALIGN 64     // a split's targets are a multiple of this
+#define MRK_TBLOCK 256         // threads of the per-query kernels
+
+namespace {
+
+struct KnnGeom {
+  int kb, q;        // the bucket of K; queries per thread
+  int64_t qtiles;   // query tiles per cloud
+  int splits;
+  int64_t per;      // targets per split
+  int chunk;        // targets staged at a time
+};
+
+KnnGeom knn_geom(int64_t N, int64_t P1, int64_t P2, int K) {
+  KnnGeom g;
+  g.kb = 1;
+  while (g.kb < K) g.kb *= 2;
+  g.q = g.kb <= 8 ? 4 : (g.kb == 16 ? 2 : 1);
+  g.qtiles = (P1 + MRK_BLOCK * g.q - 1) / (MRK_BLOCK * g.q);
+  g.splits = 1;
+  g.per = P2;
+  const int64_t groups = N * g.qtiles;
+  if (groups < MRK_CUS) {
+    int64_t want = (MRK_WANT_GROUPS + groups - 1) / groups;
+    if (want > MRK_MAXSPLIT) want = MRK_MAXSPLIT;
+    g.per = ((P2 + want - 1) / want + MRK_SPLIT_ALIGN - 1) / MRK_SPLIT_ALIGN * MRK_SPLIT_ALIGN;
+    g.splits = (int)((P2 + g.per - 1) / g.per);
+  }
+  g.chunk = (int)(g.per < MRK_MAXCHUNK ? g.per : MRK_MAXCHUNK);
+  return g;
+}
+
+// c < L[KB - 1] is known: c takes its place in the ascending list and the worst key leaves. Compile-time indices only.
+template <int KB> __device__ __forceinline__ void knn_insert(u64 (&L)[KB], u64 c) {
+#pragma unroll
+  for (int i = KB - 1; i > 0; --i) {
+    const u64 below = L[i - 1];
+    L[i] = c < below ? below : (c < L[i] ? c : L[i]);
+  }
+  L[0] = c < L[0] ? c : L[0];
+}
+
+// The first K slots of a list as dists / idx: 0 / -1 for a slot that was never filled (or a row past its length).
+template <int KB>
+__device__ __forceinline__ void knn_store(const u64 (&L)[KB], bool row_ok, int K, float* __restrict__ od,
+                                          int32_t* __restrict__ oi) {
+#pragma unroll
+  for (int s = 0; s < KB; ++s) {
+    const bool ok = row_ok && L[s] != ~0ull;
+    if (s < K) {
+      od[s] = ok ? __uint_as_float((uint32_t)(L[s] >> 32)) : 0.0f;
+      oi[s] = ok ? (int32_t)(uint32_t)L[s] : -1;
+    }
+  }
+}
+
+// grid (query tiles * splits, N). part != NULL: (N, P1, splits, K) keys; else dists / idx (N, P1, K).
+template <int NORM, int KB, int Q>
+__global__ void __launch_bounds__(MRK_BLOCK) k_knn(const float* __restrict__ p1, const float* __restrict__ p2, int64_t P1,
+                                                   int64_t P2, const int64_t* __restrict__ l1,
+                                                   const int64_t* __restrict__ l2, int K, int splits, int64_t per,
+                                                   float* __restrict__ dists, int32_t* __restrict__ idx,
+                                                   u64* __restrict__ part) {
+  __shared__ float4 sm[MRK_MAXCHUNK];
+  const int64_t n = blockIdx.y;
+  const int64_t q0 = ((int64_t)blockIdx.x / splits) * (MRK_BLOCK * Q);
+  const int s = (int)((int64_t)blockIdx.x % splits);
+  const int64_t lq = cloud_len(l1, n, P1), lt = cloud_len(l2, n, P2);
+  const float* __restrict__ q = p1 + 3 * n * P1;
+  const float* __restrict__ t = p2 + 3 * n * P2;
+  const int64_t tb = (int64_t)s * per;
+  int64_t te = tb + per < lt ? tb + per : lt;
+  if (q0 >= lq) te = tb;  // no query of this tile is inside its cloud (uniform): nothing to scan
+
+  float qx[Q], qy[Q], qz[Q];
+  u64 L[Q][KB];
+#pragma unroll
+  for (int k = 0; k < Q; ++k) {
+    const int64_t i = q0 + k * MRK_BLOCK + threadIdx.x;
+    const bool ok = i < lq;
+    qx[k] = ok ? q[3 * i] : 0.0f;
+    qy[k] = ok ? q[3 * i + 1] : 0.0f;
+    qz[k] = ok ? q[3 * i + 2] : 0.0f;
+#pragma unroll
+    for (int j = 0; j < KB; ++j) L[k][j] = ~0ull;
+  }
+  for (int64_t t0 = tb; t0 < te; t0 += MRK_MAXCHUNK) {
+    const int cnt = (int)((te - t0 < MRK_MAXCHUNK) ? te - t0 : MRK_MAXCHUNK);
+    if (t0 != tb) __syncthreads();  // the previous chunk has been read
+    for (int j = threadIdx.x; j < cnt; j += MRK_BLOCK) {
+      const float* p = t + 3 * (t0 + j);
+      sm[j] = make_float4(p[0], p[1], p[2], 0.0f);
+    }
+    __syncthreads();
+    const uint32_t base = (uint32_t)t0;
+#pragma unroll 2
+    for (int j = 0; j < cnt; ++j) {
+      const float4 p = sm[j];
+#pragma unroll
+      for (int k = 0; k < Q; ++k) {
+        // a distance is >= +0: its bits order as an unsigned integer, below the all-ones of an empty slot
+        const uint32_t b = __float_as_uint(dist3<NORM>(qx[k], qy[k], qz[k], p));
+        if (b < (uint32_t)(L[k][KB - 1] >> 32)) knn_insert<KB>(L[k], ((u64)b << 32) | (u64)(base + (uint32_t)j));
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < Q; ++k) {
+    const int64_t i = q0 + k * MRK_BLOCK + threadIdx.x;
+    if (i >= P1) continue;
+    const int64_t row = n * P1 + i;
+    if (part) {
+      u64* __restrict__ o = part + (row * splits + s) * K;
+#pragma unroll
+      for (int j = 0; j < KB; ++j) {
+        if (j < K) o[j] = i < lq ? L[k][j] : ~0ull;
+      }
+    } else {
+      knn_store<KB>(L[k], i < lq, K, dists + row * K, idx + row * K);
+    }
+  }
+}
+
+// One thread per row of (N, P1): its `splits` ascending lists of K keys -> the K smallest, decoded. A list's
+// remaining keys are skipped at its first key that does not enter.
+template <int KB>
+__global__ void __launch_bounds__(MRK_TBLOCK) k_knn_merge(const u64* __restrict__ part, int64_t rows, int K, int splits,
+                                                          float* __restrict__ dists, int32_t* __restrict__ idx) {
+  const int64_t row = (int64_t)blockIdx.x * MRK_TBLOCK + threadIdx.x;
+  if (row >= rows) return;
+  u64 L[KB];
+#pragma unroll
+  for (int j = 0; j < KB; ++j) L[j] = ~0ull;
+  for (int s = 0; s < splits; ++s) {
+    const u64* __restrict__ p = part + (row * splits + s) * K;
+    for (int j = 0; j < K; ++j) {
+      const u64 c = p[j];
+      if (!(c < L[KB - 1])) break;
+      knn_insert<KB>(L, c);
+    }
+  }
+  knn_store<KB>(L, true, K, dists + row * K, idx + row * K);
+}
+
+// grid (blocks over P1, N). fix / rem: (N, P2, 3) rows of the targets.
+template <int NORM>
+__global__ void __launch_bounds__(MRK_TBLOCK) k_knn_bwd(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                        int64_t P1, int64_t P2, const int64_t* __restrict__ l1,
+                                                        const int64_t* __restrict__ l2, int K,
+                                                        const int32_t* __restrict__ idx, const float* __restrict__ g,
+                                                        float* __restrict__ grad_p1, u64* __restrict__ fix,
+                                                        float* __restrict__ rem) {
+  const int64_t n = blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * MRK_TBLOCK + threadIdx.x;
+  if (i >= P1) return;
+  const int64_t row = n * P1 + i;
+  const int64_t lt = cloud_len(l2, n, P2);
+  const float* __restrict__ q = p1 + 3 * row;
+  float acc[3] = {0.0f, 0.0f, 0.0f};
+  if (i < cloud_len(l1, n, P1)) {
+    const float q0 = q[0], q1 = q[1], q2 = q[2];
+    for (int k = 0; k < K; ++k) {
+      const int32_t j = idx[row * K + k];
+      if (j < 0 || j >= lt) continue;
+      const float up = g[row * K + k];
+      const float* __restrict__ t = p2 + 3 * (n * P2 + j);
+      const float df[3] = {q0 - t[0], q1 - t[1], q2 - t[2]};
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float v = NORM == 2 ? (2.0f * up) * df[c] : up * sgn(df[c]);
+        acc[c] += v;
+        fix_add(fix, rem, 3 * (n * P2 + j) + c, v);
+      }
+    }
+  }
+  grad_p1[3 * row] = acc[0];
+  grad_p1[3 * row + 1] = acc[1];
+  grad_p1[3 * row + 2] = acc[2];
+}
+
+__global__ void __launch_bounds__(MRK_TBLOCK) k_knn_bwd_p2(const u64* __restrict__ fix, const float* __restrict__ rem,
+                                                           int64_t n, float* __restrict__ grad_p2) {
+  const int64_t i = (int64_t)blockIdx.x * MRK_TBLOCK + threadIdx.x;
+  if (i < n) grad_p2[i] = 0.0f - fix_read(fix, rem, i);  // +0 for a target nothing reached
+}
+
+int check_knn(const char* who, const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2, int32_t norm,
+              int32_t K) {
+  if (N < 1 || P1 < 1 || P2 < 1) return set_err(MR_EINVAL, "%s: N, P1 and P2 must be >= 1", who);
+  if (K < 1) return set_err(MR_EINVAL, "%s: K must be >= 1", who);
+  if (K > MRK_MAXK) return set_err(MR_EUNSUPPORTED, "%s: K > %d is not built", who, MRK_MAXK);
+  if (!sizes_ok(N, P1, P2))
+    return set_err(MR_EUNSUPPORTED, "%s: more than 65535 clouds or clouds too large for 32-bit point ids", who);
+  if (norm != 1 && norm != 2) return set_err(MR_EINVAL, "%s: norm must be 1 or 2", who);
+  if (!p1 || !p2) return set_err(MR_EINVAL, "%s: p1 / p2 is NULL", who);
+  return MR_OK;
+}
+
+size_t knn_part_bytes(int64_t N, int64_t P1, int K, const KnnGeom& g) {
+  return g.splits > 1 ? sizeof(u64) * (size_t)(N * P1) * (size_t)K * (size_t)g.splits : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t mr_knn_geometry(int64_t N, int64_t P1, int64_t P2, int32_t K, int32_t* queries_per_group, int32_t* splits,
+                        int32_t* lds_chunk) {
+  if (N < 1 || P1 < 1 || P2 < 1 || K < 1) return set_err(MR_EINVAL, "knn geometry: N, P1, P2 and K must be >= 1");
+  if (K > MRK_MAXK) return set_err(MR_EUNSUPPORTED, "knn geometry: K > %d is not built", MRK_MAXK);
+  if (!sizes_ok(N, P1, P2))
+    return set_err(MR_EUNSUPPORTED, "knn geometry: more than 65535 clouds or clouds too large for 32-bit point ids");
+  const KnnGeom g = knn_geom(N, P1, P2, K);
+  if (queries_per_group) *queries_per_group = MRK_BLOCK * g.q;
+  if (splits) *splits = g.splits;
+  if (lds_chunk) *lds_chunk = g.chunk;
+  return MR_OK;
+}
+
+size_t mr_knn_points_workspace(int64_t N, int64_t P1, int64_t P2, int32_t K) {
+  if (!sizes_ok(N, P1, P2) || K < 1 || K > MRK_MAXK) return 0;
+  Carver c(nullptr);
+  c.take<u64>(knn_part_bytes(N, P1, K, knn_geom(N, P1, P2, K)) / sizeof(u64) + 1);  // never 0: 0 means out of range
+  return c.off;
+}
+
+int32_t mr_knn_points(const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2, const int64_t* lengths1,
+                      const int64_t* lengths2, int32_t norm, int32_t K, float* dists, int32_t* idx, void* ws,
+                      size_t ws_bytes, void* stream) {
+  if (int rc = check_knn("knn points", p1, p2, N, P1, P2, norm, K)) return rc;
+  if (!dists || !idx || !ws) return set_err(MR_EINVAL, "knn points: dists / idx / workspace is NULL");
+  if (ws_bytes < mr_knn_points_workspace(N, P1, P2, K)) return set_err(MR_EWORKSPACE, "knn points workspace too small");
+  const KnnGeom g = knn_geom(N, P1, P2, K);
+  const hipStream_t st = (hipStream_t)stream;
+  u64* part = g.splits > 1 ? (u64*)ws : nullptr;
+  const dim3 grid((unsigned)(g.qtiles * g.splits), (unsigned)N);
+  const int k = K, splits = g.splits;
+  int rc;
+#define MRK_SCAN(NORM, KB, Q)                                                                                         \
+  rc = launch(KID_NONE, "k_knn", k_knn<NORM, KB, Q>, grid, MRK_BLOCK, 0, st, p1, p2, P1, P2, lengths1, lengths2, k, splits, \
+              g.per, dists, idx, part)
+#define MRK_SCAN_K(NORM)            \
+  switch (g.kb) {                   \
+    case 1: MRK_SCAN(NORM, 1, 4); break;   \
+    case 2: MRK_SCAN(NORM, 2, 4); break;   \
+    case 4: MRK_SCAN(NORM, 4, 4); break;   \
+    case 8: MRK_SCAN(NORM, 8, 4); break;   \
+    case 16: MRK_SCAN(NORM, 16, 2); break; \
+    default: MRK_SCAN(NORM, 32, 1); break; \
+  }
+  if (norm == 2) {
+    MRK_SCAN_K(2)
+  } else {
+    MRK_SCAN_K(1)
+  }
+#undef MRK_SCAN_K
+#undef MRK_SCAN
+  if (rc || !part) return rc;
+  const int64_t rows = N * P1;
+  const unsigned mg = (unsigned)((rows + MRK_TBLOCK - 1) / MRK_TBLOCK);
+#define MRK_MERGE(KB)                                                                                            \
+  case KB:                                                                                                       \
+    return launch(KID_NONE, "k_knn_merge", k_knn_merge<KB>, mg, MRK_TBLOCK, 0, st, (const u64*)part, rows, k, splits, dists, \
+                  idx)
+  switch (g.kb) {
+    MRK_MERGE(1);
+    MRK_MERGE(2);
+    MRK_MERGE(4);
+    MRK_MERGE(8);
+    MRK_MERGE(16);
+    default:
+    MRK_MERGE(32);
+  }
+#undef MRK_MERGE
+}
+
+size_t mr_knn_points_backward_workspace(int64_t N, int64_t P1, int64_t P2, int32_t K) {
+  if (!sizes_ok(N, P1, P2) || K < 1 || K > MRK_MAXK) return 0;
+  return carve_fix(nullptr, 3 * N * P2).bytes;
+}
+
+int32_t mr_knn_points_backward(const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2,
+                               const int64_t* lengths1, const int64_t* lengths2, int32_t norm, int32_t K,
+                               const int32_t* idx, const float* grad_dists, float* grad_p1, float* grad_p2, void* ws,
+                               size_t ws_bytes, void* stream) {
+  if (int rc = check_knn("knn points backward", p1, p2, N, P1, P2, norm, K)) return rc;
+  if (!idx || !grad_dists || !grad_p1 || !grad_p2 || !ws) return set_err(MR_EINVAL, "knn points backward: NULL pointer");
+  const FixWS w = carve_fix(ws, 3 * N * P2);
+  if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "knn points backward workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  if (int rc = memset_async(ws, 0, w.bytes, st)) return rc;
+  const dim3 grid((unsigned)ceil_div(P1, MRK_TBLOCK), (unsigned)N);
+  const int k = K;
+  if (int rc = launch(KID_NONE, "k_knn_bwd", norm == 2 ? k_knn_bwd<2> : k_knn_bwd<1>, grid, MRK_TBLOCK, 0, st, p1, p2, P1, P2,
+                      lengths1, lengths2, k, idx, grad_dists, grad_p1, w.fix, w.rem))
+    return rc;
+  return launch(KID_NONE, "k_knn_bwd_p2", k_knn_bwd_p2, (unsigned)ceil_div(3 * N * P2, MRK_TBLOCK), MRK_TBLOCK, 0, st,
+                (const u64*)w.fix, (const float*)w.rem, 3 * N * P2, grad_p2);
+}
+
+}  // extern "C"

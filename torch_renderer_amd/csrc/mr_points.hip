@@ -36,6 +36,7 @@
 #include "../../include/mi355r.h"
 #include "mr_common.h"
 #include "mr_host.h"
+#include "mr_cloud.h"
 
 #define MRN_BLOCK 128                  // threads of a k_nn workgroup (two waves)
 #define MRN_Q 4                        // queries per thread
@@ -49,20 +50,12 @@
 
 namespace {
 
-typedef unsigned long long u64;
-
 struct NNGeom {
   int64_t N, P[2];     // clouds; points of x and of y (padded)
   int chunk[2];        // targets per workgroup of direction d (d = 0: queries x, targets y)
   int64_t nchunk[2];   // chunks of direction d
   int64_t groups[2];   // workgroups of direction d per cloud
 };
-
-bool sizes_ok(int64_t N, int64_t P1, int64_t P2) {
-  // per-cloud indices are int32; the grid's y dimension is the batch
-  return N >= 1 && P1 >= 1 && P2 >= 1 && N <= 65535 && P1 < 0x7fffffffll && P2 < 0x7fffffffll &&
-         N * P1 < (1ll << 40) / 3 && N * P2 < (1ll << 40) / 3;
-}
 
 NNGeom nn_geom(int64_t N, int64_t P1, int64_t P2, int64_t want_groups = MRN_WANT_GROUPS) {
   NNGeom g;
@@ -100,33 +93,6 @@ PointsWS carve_points(void* base, int64_t N, int64_t P1, int64_t P2) {
   w.part = c.take<double>(2 * (size_t)(N * w.nblk));
   w.bytes = c.off;
   return w;
-}
-
-// Fixed-point rows of a scatter's targets: `n` 64-bit words, then `n` float remainders.
-struct FixWS {
-  u64* fix;
-  float* rem;
-  size_t bytes;
-};
-FixWS carve_fix(void* base, int64_t n) {
-  FixWS w;
-  Carver c(base);
-  w.fix = c.take_packed<u64>((size_t)n);  // words and remainders back to back: one memset
-  w.rem = c.take<float>((size_t)n);
-  w.bytes = c.off;
-  return w;
-}
-
-__device__ __forceinline__ int64_t cloud_len(const int64_t* __restrict__ lengths, int64_t n, int64_t P) {
-  if (!lengths) return P;
-  const int64_t l = lengths[n];
-  return l < 0 ? 0 : (l > P ? P : l);
-}
-
-template <int NORM> __device__ __forceinline__ float dist3(float qx, float qy, float qz, float4 t) {
-  const float dx = qx - t.x, dy = qy - t.y, dz = qz - t.z;
-  if (NORM == 2) return (dx * dx + dy * dy) + dz * dz;
-  return (fabsf(dx) + fabsf(dy)) + fabsf(dz);
 }
 
 template <int NORM>
@@ -255,8 +221,6 @@ __global__ void __launch_bounds__(MRR_BLOCK) k_cham_final(const double* __restri
   total = block_sum(total, sm);
   if (!per_cloud && threadIdx.x == 0) out[0] = (float)(total * scale);
 }
-
-__device__ __forceinline__ float sgn(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }
 
 // grid (blocks over max(P1, P2), N, directions): point i of direction d's queries adds its difference to its
 // target's row. fix / rem: (N, P1, 3) rows of x then (N, P2, 3) rows of y.

@@ -314,6 +314,81 @@ class ChamferDistance(torch.autograd.Function):
         return gx.to(xdt), gy.to(ydt), None, None, None, None, None
 
 
+# --------------------------------------------------------------------------- K nearest neighbours (csrc/mr_knn.hip)
+KNN_MAX_K = 32
+
+
+def _knn_k(K):
+    K = int(K)
+    if K < 1:
+        raise ValueError("K must be >= 1")
+    if K > KNN_MAX_K:
+        raise NotImplementedError(f"knn_points: K > {KNN_MAX_K} is not built")
+    return K
+
+
+def knn_geometry(N, P1, P2, K):
+    """(queries_per_group, splits, lds_chunk) of the launch mr_knn_points makes for these shapes (host only)."""
+    out = [ctypes.c_int32() for _ in range(3)]
+    check(_lib.load().mr_knn_geometry(int(N), int(P1), int(P2), _knn_k(K), *(ctypes.byref(o) for o in out)))
+    return tuple(o.value for o in out)
+
+
+def _knn_forward(p1f, p2f, l1, l2, N, P1, P2, K, norm):
+    L = _lib.load()
+    dev = p1f.device
+    dists = torch.empty((N, P1, K), device=dev)
+    idx = torch.empty((N, P1, K), dtype=torch.int32, device=dev)
+    wsb = _ws_size(L.mr_knn_points_workspace, N, P1, P2, K)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    check(L.mr_knn_points(ptr(p1f), ptr(p2f), N, P1, P2, ptr(l1), ptr(l2), int(norm), K, ptr(dists), ptr(idx), ptr(ws),
+                          wsb, _lib.stream_handle(dev)))
+    return dists, idx
+
+
+def knn_points(p1, p2, lengths1=None, lengths2=None, K=1, norm=2):
+    """(dists (N,P1,K) float32, idx (N,P1,K) int32): for every point of p1 (N,P1,3) its K nearest points of
+    p2[n, :lengths2[n]], ascending by (distance, index), with nearest_points' distance; equal distances take the
+    lower index. Slots k >= min(K, lengths2[n]) and rows past lengths1[n] are 0 / -1. 1 <= K <= 32. No autograd; one
+    launch, or a scan and a merge when the shapes alone cannot fill the chip (mr_knn_points)."""
+    K = _knn_k(K)
+    p1f, p2f, l1, l2, N, P1, P2 = _cloud_args(p1, p2, lengths1, lengths2, norm)
+    return _knn_forward(p1f, p2f, l1, l2, N, P1, P2, K, norm)
+
+
+class KnnPoints(torch.autograd.Function):
+    """knn_points with the gradient of ``dists`` w.r.t. p1 and p2 (``idx`` is not differentiable): one memset and two
+    launches backward, the many-to-one p2 side summed in fixed point (mr_knn_points_backward)."""
+
+    @staticmethod
+    def forward(ctx, p1, p2, lengths1, lengths2, K, norm):
+        K = _knn_k(K)
+        p1f, p2f, l1, l2, N, P1, P2 = _cloud_args(p1, p2, lengths1, lengths2, norm)
+        dists, idx = _knn_forward(p1f, p2f, l1, l2, N, P1, P2, K, norm)
+        ctx.mark_non_differentiable(idx)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(p1f, p2f, idx, l1, l2)
+        ctx.args = (K, int(norm), p1.dtype, p2.dtype)
+        return dists, idx
+
+    @staticmethod
+    def backward(ctx, g, _g_idx):
+        if g is None:
+            return (None,) * 6
+        p1f, p2f, idx, l1, l2 = ctx.saved_tensors
+        K, norm, dt1, dt2 = ctx.args
+        g = g.detach().float().contiguous()
+        _require_cuda(g)
+        L = _lib.load()
+        N, P1, P2 = p1f.shape[0], p1f.shape[1], p2f.shape[1]
+        g1, g2 = torch.empty_like(p1f), torch.empty_like(p2f)
+        wsb = _ws_size(L.mr_knn_points_backward_workspace, N, P1, P2, K)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=p1f.device)
+        check(L.mr_knn_points_backward(ptr(p1f), ptr(p2f), N, P1, P2, ptr(l1), ptr(l2), norm, K, ptr(idx), ptr(g),
+                                       ptr(g1), ptr(g2), ptr(ws), wsb, _lib.stream_handle(p1f.device)))
+        return g1.to(dt1), g2.to(dt2), None, None, None, None
+
+
 def _one_cloud(t, name):
     """A (P,3) or (1,P,3) cloud as a contiguous float32 (P,3) tensor."""
     if t.dim() == 3 and t.shape[0] == 1:

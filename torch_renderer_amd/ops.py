@@ -10,6 +10,8 @@ The random draws are torch calls on the meshes' device — ``torch.multinomial``
 pytorch3d_icp_evaluation.py) take (N, P, 3) tensors or ``Pointclouds``; the ICP loop, its nearest-neighbour search,
 the Procrustes solve and the convergence test run on the device (kernels.icp / kernels.points_alignment, the
 k_icp_* kernels of csrc/mr_points.hip). Neither is differentiable.
+
+``knn_points`` (K <= 32 nearest neighbours, csrc/mr_knn.hip; ``dists`` is differentiable) and ``knn_gather``.
 """
 from __future__ import annotations
 
@@ -197,3 +199,52 @@ def sample_points_from_meshes(meshes, num_samples: int = 10000, return_normals: 
                 face_idx[torch.tensor(valid, device=dev)] = drawn
         uv = torch.rand(2, N, S, device=dev)
     return SamplePoints.apply(verts, faces, face_idx, uv)
+
+
+class _KNN(NamedTuple):
+    dists: torch.Tensor
+    idx: torch.Tensor
+    knn: Optional[torch.Tensor]
+
+
+def knn_gather(x, idx, lengths=None):
+    """x (N,M,U) gathered at idx (N,L,K): (N,L,K,U), out[n,l,k] = x[n, idx[n,l,k]] (a torch gather: differentiable
+    w.r.t. x). With ``lengths`` (N,), entries k >= lengths[n] are zero (knn_points pads their idx with 0)."""
+    N, M, U = x.shape
+    _N, L, K = idx.shape
+    if N != _N:
+        raise ValueError("x and idx must have same batch dimension.")
+    if lengths is not None and tuple(lengths.shape) != (N,):
+        raise ValueError("lengths must be of shape (N,)")
+    out = x[:, :, None].expand(-1, -1, K, -1).gather(1, idx.long()[..., None].expand(-1, -1, -1, U))
+    if lengths is None and M >= K:
+        return out
+    # nothing is read back from the device: the mask is applied whether or not a length is below K
+    lengths = torch.full((N,), M, device=x.device) if lengths is None else lengths.to(x.device)
+    pad = torch.arange(K, device=x.device)[None, :] >= lengths[:, None]  # (N,K)
+    return out.masked_fill(pad[:, None, :, None].expand(-1, L, -1, U), 0.0)
+
+
+def knn_points(p1, p2, lengths1=None, lengths2=None, norm: int = 2, K: int = 1, version: int = -1,
+               return_nn: bool = False, return_sorted: bool = True):
+    """``pytorch3d.ops.knn_points``: for every point of p1 (N,P1,3) its K <= 32 nearest points of p2 (N,P2,3), as a
+    namedtuple (dists (N,P1,K), idx (N,P1,K) int64, knn (N,P1,K,3) or None). dists is the squared L2 (norm 2) or L1
+    (norm 1) distance in float32, ascending; equal distances take the lower index. Entries past min(K, lengths2[n])
+    and rows past lengths1[n] are padded with 0 in both. The output is always sorted (a valid answer for
+    ``return_sorted=False``); ``version`` is accepted and ignored. dists is differentiable w.r.t. p1 and p2
+    (kernels.KnnPoints, csrc/mr_knn.hip), knn through the gather."""
+    if p1.dim() != 3 or p2.dim() != 3:
+        raise ValueError("pts1 and pts2 must be (N, P, D) tensors.")
+    if p1.shape[0] != p2.shape[0]:
+        raise ValueError("pts1 and pts2 must have the same batch dimension.")
+    if p1.shape[2] != p2.shape[2]:
+        raise ValueError("pts1 and pts2 must have the same point dimension.")
+    if norm not in (1, 2):
+        raise ValueError("Support for 1 or 2 norm.")
+    for l in (lengths1, lengths2):
+        if l is not None and tuple(l.shape) != (p1.shape[0],):
+            raise ValueError("lengths must be of shape (N,)")
+    dists, idx = kernels.KnnPoints.apply(p1, p2, lengths1, lengths2, K, norm)
+    dists = dists.to(p1.dtype)
+    idx = idx.clamp(min=0).long()
+    return _KNN(dists=dists, idx=idx, knn=knn_gather(p2, idx, lengths2) if return_nn else None)
