@@ -681,6 +681,27 @@ int32_t mr_knn_points_backward(const float* p1, const float* p2, int64_t N, int6
 int32_t mr_knn_geometry(int64_t N, int64_t P1, int64_t P2, int32_t K, int32_t* queries_per_group, int32_t* splits,
                         int32_t* lds_chunk);
 
+/* Farthest-point subsampling (PyTorch3D sample_farthest_points) of points (N,P,3). Per cloud n, with L = lengths[n]
+ * (NULL: P; clamped to [0, P]) and k_n = min(K_per_cloud[n], L) (K_per_cloud NULL: Kmax; clamped to [0, Kmax]): the
+ * first index is start_idx[n] (NULL: 0; clamped into the cloud); every point p < L carries m[p] = +inf; after each
+ * selection s, m[p] = min(m[p], d(p, s)) with the float32 squared distance of the chamfer calls above, and the next
+ * index is the p < L with the largest m[p], the lowest index among equal values (a selected point stays in the
+ * running with m = 0). idx (N,Kmax) int32 and pts (N,Kmax,3) float32, the selected points' coordinates; the slots
+ * k >= k_n are -1 / 0. lengths, K_per_cloud and start_idx are int64 (N,) device arrays.
+ * One launch, one workgroup per cloud for all of its rounds, nothing between workgroups; no memset, no atomics;
+ * bitwise reproducible. Up to 1,024 * 32 points a cloud lives in its workgroup's registers (and, at 32 points a
+ * thread, its m values in LDS); above, the points are read from global memory every round and m lives in the
+ * workspace (N * P floats): correct, and slow. mr_farthest_points_geometry (host only) returns what the launch would
+ * use: threads per workgroup, points per thread (register path: the bucket 1, 2, 4, ..., 32) and whether the cloud is
+ * streamed (each pointer may be NULL). MR_EINVAL for NULL or non-positive sizes, MR_EUNSUPPORTED for clouds too
+ * large for 32-bit point ids, MR_EWORKSPACE; all before any GPU call. */
+int32_t mr_farthest_points_geometry(int64_t N, int64_t P, int64_t Kmax, int32_t* threads, int32_t* points_per_thread,
+                                    int32_t* streamed);
+size_t mr_farthest_points_workspace(int64_t N, int64_t P, int64_t Kmax);
+int32_t mr_farthest_points(const float* points, int64_t N, int64_t P, const int64_t* lengths, const int64_t* K_per_cloud,
+                           int64_t Kmax, const int64_t* start_idx, int32_t* idx, float* pts, void* ws, size_t ws_bytes,
+                           void* stream);
+
 /* Per-kernel timing with HIP events recorded on each launch's stream (bench.py).
  * enable=1 clears and starts collection; mr_timing_read synchronizes on the
  * recorded events and returns, per kernel id, launches and summed ms. */

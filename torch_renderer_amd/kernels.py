@@ -389,6 +389,93 @@ class KnnPoints(torch.autograd.Function):
         return g1.to(dt1), g2.to(dt2), None, None, None, None
 
 
+# --------------------------------------------------------------------------- farthest points (csrc/mr_fps.hip)
+def farthest_geometry(N, P, Kmax):
+    """(threads, points_per_thread, streamed) of the launch mr_farthest_points makes for these shapes (host only):
+    the workgroup size, the points a thread keeps in registers (the bucket 1, 2, 4, ..., 32; for a streamed cloud
+    the points a thread walks every round), and whether the cloud is too large for the registers."""
+    out = [ctypes.c_int32() for _ in range(3)]
+    check(_lib.load().mr_farthest_points_geometry(int(N), int(P), int(Kmax), *(ctypes.byref(o) for o in out)))
+    return out[0].value, out[1].value, bool(out[2].value)
+
+
+def _farthest_args(points, lengths, K, start_idx, Kmax):
+    """The checked inputs of a farthest-points call: (float32 points, lengths, K per cloud or None, start, N, P, Kmax)."""
+    if points.dim() != 3:
+        raise ValueError("farthest points: points must be an (N, P, D) tensor")
+    if points.shape[2] != 3:
+        raise NotImplementedError("farthest points: only D = 3 is built")
+    N, P = points.shape[0], points.shape[1]
+    if N < 1 or P < 1:
+        raise ValueError("farthest points: N and P must be >= 1")
+    kper = None
+    if torch.is_tensor(K):
+        if tuple(K.shape) != (N,):
+            raise ValueError("K and points must have the same batch dimension")
+        kper = K
+        Kmax = int(K.max()) if Kmax is None else int(Kmax)  # the one host read of a device K
+    else:
+        Kmax = int(K)
+    if Kmax < 1:
+        raise ValueError("farthest points: the output width max(K) must be >= 1")
+    for name, t in (("lengths", lengths), ("start_idx", start_idx)):
+        if t is not None and tuple(t.shape) != (N,):
+            raise ValueError(f"farthest points: {name} must be of shape (N,)")
+    _require_cuda(points, lengths, kper, start_idx)
+    i64 = [None if t is None else t.detach().to(torch.int64).contiguous() for t in (lengths, kper, start_idx)]
+    return (points.detach().float().contiguous(), *i64, N, P, Kmax)
+
+
+def farthest_points(points, lengths=None, K=50, start_idx=None, Kmax=None):
+    """(idx (N,Kmax) int32, pts (N,Kmax,3) float32): farthest-point subsampling of points (N,P,3) by the rule of
+    mr_farthest_points (include/mi355r.h): cloud n starts at ``start_idx[n]`` (None: 0) and selects min(K[n],
+    lengths[n]) points, each the one farthest (float32 squared distance, fixed operation order) from those selected
+    so far, the lowest index among equal distances; ``pts`` are their coordinates and the unused slots are -1 / 0.
+    ``K`` is an int or an (N,) tensor; ``Kmax`` (the output width) saves the host read of a tensor ``K``'s maximum.
+    No autograd; one launch, one workgroup per cloud, nothing synchronises."""
+    pf, l, kper, st, N, P, Kmax = _farthest_args(points, lengths, K, start_idx, Kmax)
+    L = _lib.load()
+    dev = pf.device
+    idx = torch.empty((N, Kmax), dtype=torch.int32, device=dev)
+    pts = torch.empty((N, Kmax, 3), device=dev)
+    wsb = _ws_size(L.mr_farthest_points_workspace, N, P, Kmax)
+    if wsb == 0:
+        raise NotImplementedError("mi355r: farthest points: clouds too large for 32-bit point ids")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    check(L.mr_farthest_points(ptr(pf), N, P, ptr(l), ptr(kper), Kmax, ptr(st), ptr(idx), ptr(pts), ptr(ws), wsb,
+                               _lib.stream_handle(dev)))
+    return idx, pts
+
+
+class FarthestPoints(torch.autograd.Function):
+    """farthest_points as an autograd node: (pts, idx), ``idx`` not differentiable, ``pts`` differentiable w.r.t.
+    ``points``. The forward returns the coordinates the kernel holds; the backward scatters the upstream gradient
+    to the selected rows with torch's ``index_put_(accumulate=True)`` (a row selected more than once takes the sum;
+    the padded slots add zeros to row 0). No backward kernel."""
+
+    @staticmethod
+    def forward(ctx, points, lengths, K, start_idx, Kmax):
+        idx, pts = farthest_points(points, lengths, K, start_idx, Kmax)
+        ctx.mark_non_differentiable(idx)
+        ctx.set_materialize_grads(False)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(idx)
+            ctx.args = (tuple(points.shape), points.dtype)
+        return pts, idx
+
+    @staticmethod
+    def backward(ctx, g, _g_idx):
+        if g is None:
+            return (None,) * 5
+        (idx,) = ctx.saved_tensors
+        shape, dtype = ctx.args
+        g = g.detach().to(dtype).masked_fill((idx < 0)[..., None], 0)
+        grad = torch.zeros(shape, dtype=dtype, device=g.device)
+        rows = torch.arange(shape[0], device=g.device)[:, None].expand_as(idx)
+        grad.index_put_((rows, idx.clamp(min=0).long()), g, accumulate=True)
+        return grad, None, None, None, None
+
+
 def _one_cloud(t, name):
     """A (P,3) or (1,P,3) cloud as a contiguous float32 (P,3) tensor."""
     if t.dim() == 3 and t.shape[0] == 1:

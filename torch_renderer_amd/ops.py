@@ -12,6 +12,9 @@ the Procrustes solve and the convergence test run on the device (kernels.icp / k
 k_icp_* kernels of csrc/mr_points.hip). Neither is differentiable.
 
 ``knn_points`` (K <= 32 nearest neighbours, csrc/mr_knn.hip; ``dists`` is differentiable) and ``knn_gather``.
+
+``sample_farthest_points`` (csrc/mr_fps.hip): one workgroup per cloud runs all K rounds on the device; the selected
+points are differentiable w.r.t. the input points.
 """
 from __future__ import annotations
 
@@ -248,3 +251,78 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, norm: int = 2, K: int = 1, 
     dists = dists.to(p1.dtype)
     idx = idx.clamp(min=0).long()
     return _KNN(dists=dists, idx=idx, knn=knn_gather(p2, idx, lengths2) if return_nn else None)
+
+
+def sample_farthest_points(points, lengths=None, K=50, random_start_point: bool = False):
+    """``pytorch3d.ops.sample_farthest_points``: (selected_points (N,Kmax,3) in ``points``' dtype, selected_idx
+    (N,Kmax) int64) of an (N,P,3) tensor with optional ``lengths`` (N,), or of a ``Pointclouds`` (whose lengths are
+    then the clouds' own; an explicit ``lengths`` beside it raises ValueError). ``K`` is an int, a list of N ints or an
+    (N,) integer tensor, and Kmax = max(K).
+
+    Per cloud n, with L = lengths[n] and k_n = min(K[n], L): the first index is 0, or with ``random_start_point`` a
+    draw in [0, L) made on the device from torch's generator (``torch.manual_seed`` reproduces it; the draws are not
+    upstream's). Every point p < L carries m[p] = +inf; after each selection s, m[p] = min(m[p], |p - s|^2) in
+    float32 with the operation order (dx*dx + dy*dy) + dz*dz, and the next index is the p < L with the largest m[p],
+    the lowest index among equal values. A selected point stays in the running with m = 0, so a cloud with fewer
+    distinct points than k_n re-selects its lowest duplicate. Slots k >= k_n are -1 in selected_idx and 0 in
+    selected_points; Kmax == 0 gives empty tensors. Coordinates are read as float32 (a float64 input is rounded).
+
+    selected_points is differentiable w.r.t. ``points`` (kernels.FarthestPoints); selected_idx is not. Given lengths
+    are checked on the host, and a device tensor ``K`` costs one host read for Kmax; with an int ``K``, no
+    ``lengths`` and no ``random_start_point`` nothing synchronises and the call captures into a HIP graph. One
+    workgroup owns a cloud for all of its rounds: a batch of fewer clouds than the chip has compute units leaves the
+    rest idle, and a cloud above 32,768 points is streamed from global memory every round, which is correct and slow
+    (kernels.farthest_geometry tells)."""
+    if isinstance(points, Pointclouds):
+        if lengths is not None:
+            raise ValueError("lengths must be None for a Pointclouds input: the lengths are the clouds'")
+        padded = points.points_padded()
+        if not all(c == padded.shape[1] for c in points.counts()):
+            lengths = points.num_points_per_cloud()
+        points = padded
+    elif not torch.is_tensor(points):
+        raise ValueError("sample_farthest_points: points is an (N, P, 3) tensor or a Pointclouds")
+    if points.dim() != 3:
+        raise ValueError("sample_farthest_points: points must be an (N, P, D) tensor")
+    N, P, D = points.shape
+    if lengths is not None:
+        if tuple(lengths.shape) != (N,):
+            raise ValueError("points and lengths must have same batch dimension.")
+        if N and int(lengths.max()) > P:  # reads the lengths on the host
+            raise ValueError("A value in lengths was too large.")
+        if N and int(lengths.min()) < 0:
+            raise ValueError("sample_farthest_points: a value in lengths is negative")
+    if torch.is_tensor(K):
+        if tuple(K.shape) != (N,):
+            raise ValueError("K and points must have the same batch dimension")
+        if K.dtype.is_floating_point or K.dtype == torch.bool:
+            raise ValueError("sample_farthest_points: a tensor K must hold integers")
+        kmin, Kmax = (int(K.min()), int(K.max())) if N else (0, 0)  # the host read of a device K
+    elif isinstance(K, (list, tuple)):
+        if len(K) != N:
+            raise ValueError("K and points must have the same batch dimension")
+        kmin, Kmax = (min(int(k) for k in K), max(int(k) for k in K)) if N else (0, 0)
+    else:
+        kmin = Kmax = int(K)
+    if kmin < 0:
+        raise ValueError("sample_farthest_points: K must be >= 0")
+    if D != 3:
+        raise NotImplementedError("sample_farthest_points: only D = 3 is built")
+    _require_cuda(points, lengths)
+    dev = points.device
+    if N == 0 or P == 0 or Kmax == 0:
+        return points.new_zeros((N, Kmax, 3)), torch.full((N, Kmax), -1, dtype=torch.int64, device=dev)
+    if isinstance(K, (list, tuple)):
+        K = torch.tensor([int(k) for k in K], dtype=torch.int64, device=dev)
+    elif torch.is_tensor(K):
+        K = K.to(dev)  # a host tensor K is as good as a list
+    else:
+        K = Kmax
+    start = None
+    if random_start_point:
+        with torch.no_grad():  # one draw per cloud on the device: floor(u * L), u in [0, 1) float64
+            u = torch.rand(N, dtype=torch.float64, device=dev)
+            span = torch.full((N,), float(P), dtype=torch.float64, device=dev) if lengths is None else lengths.double()
+            start = torch.minimum((u * span).long(), span.long() - 1)
+    pts, idx = kernels.FarthestPoints.apply(points, lengths, K, start, Kmax)
+    return pts.to(points.dtype), idx.long()
