@@ -1,15 +1,14 @@
 // mi355r — K nearest neighbours of point clouds (PyTorch3D knn_points, 1 <= K <= 32) and the gradient of their
 // distances: mr_knn_points / mr_knn_points_backward / mr_knn_geometry of include/mi355r.h.
 //
-//   k_knn         a workgroup of 128 threads owns a tile of queries (Q per thread, in registers) and scans a range of
-//                 its cloud's targets itself, in ascending LDS chunks of <= 1024 float4 read as a broadcast (k_posed_nn's
-//                 shape). Every query keeps its KB smallest keys, (float bits of dist) << 32 | target index, ascending
-//                 in registers: KB is the compile-time bucket (1, 2, 4, 8, 16, 32) the requested K rounds up to, and Q
-//                 = 4, 4, 4, 4, 2, 1 keeps the lists at <= 64 VGPRs. A candidate costs one compare, its distance bits
-//                 against the high word of the worst kept key (targets arrive in ascending index order, so an equal
-//                 distance never displaces a kept key: ties go to the lowest index); only a smaller one runs the
-//                 unrolled insertion. With splits == 1 the range is the whole cloud and the workgroup writes dists / idx
-//                 itself: no key buffer, memset, atomic or merge. Only when N * query tiles < 256 (the CUs) is the
+//   k_knn         a workgroup owns a tile of queries (Q per thread) and scans a range of its cloud's targets itself, in
+//                 ascending LDS chunks (the query load and the staging of mr_cloud.h's scan, k_posed_nn's shape). Every
+//                 query keeps its KB smallest keys (nn_key) ascending in registers: KB is the compile-time bucket (1, 2,
+//                 4, 8, 16, 32) the requested K rounds up to, and Q = 4, 4, 4, 4, 2, 1 keeps the lists at <= 64 VGPRs.
+//                 A candidate costs one compare, its distance bits against those of the worst kept key (targets arrive
+//                 in ascending index order, so an equal distance never displaces a kept key: ties go to the lowest
+//                 index); only a smaller one runs the unrolled insertion. With splits == 1 the range is the whole
+//                 cloud and the workgroup writes dists / idx itself: no key buffer, memset, atomic or merge. Only when N * query tiles < 256 (the CUs) is the
 //                 target range cut into <= 16 splits, from the shapes alone; a workgroup then writes its K sorted keys
 //                 per query into the workspace (8 K splits bytes per query) and
 //   k_knn_merge   (one thread per query) merges a query's partial lists by key with the same insertion and decodes.
@@ -25,8 +24,6 @@
 #include "mr_host.h"
 #include "mr_cloud.h"
 
-#define MRK_BLOCK 128          // threads of a k_knn workgroup (two waves)
-#define MRK_MAXCHUNK 1024      // targets staged at a time (16 KiB of LDS)
 #define MRK_MAXK 32
 #define MRK_MAXSPLIT 16
 #define MRK_CUS 256            // fewer (cloud, query tile) pairs than this: the target range is split
@@ -49,7 +46,7 @@ KnnGeom knn_geom(int64_t N, int64_t P1, int64_t P2, int K) {
   g.kb = 1;
   while (g.kb < K) g.kb *= 2;
   g.q = g.kb <= 8 ? 4 : (g.kb == 16 ? 2 : 1);
-  g.qtiles = (P1 + MRK_BLOCK * g.q - 1) / (MRK_BLOCK * g.q);
+  g.qtiles = (P1 + MRN_BLOCK * g.q - 1) / (MRN_BLOCK * g.q);
   g.splits = 1;
   g.per = P2;
   const int64_t groups = N * g.qtiles;
@@ -59,7 +56,7 @@ KnnGeom knn_geom(int64_t N, int64_t P1, int64_t P2, int K) {
     g.per = ((P2 + want - 1) / want + MRK_SPLIT_ALIGN - 1) / MRK_SPLIT_ALIGN * MRK_SPLIT_ALIGN;
     g.splits = (int)((P2 + g.per - 1) / g.per);
   }
-  g.chunk = (int)(g.per < MRK_MAXCHUNK ? g.per : MRK_MAXCHUNK);
+  g.chunk = (int)(g.per < MRN_MAXCHUNK ? g.per : MRN_MAXCHUNK);
   return g;
 }
 
@@ -81,22 +78,22 @@ __device__ __forceinline__ void knn_store(const u64 (&L)[KB], bool row_ok, int K
   for (int s = 0; s < KB; ++s) {
     const bool ok = row_ok && L[s] != ~0ull;
     if (s < K) {
-      od[s] = ok ? __uint_as_float((uint32_t)(L[s] >> 32)) : 0.0f;
-      oi[s] = ok ? (int32_t)(uint32_t)L[s] : -1;
+      od[s] = ok ? key_dist(L[s]) : 0.0f;
+      oi[s] = ok ? (int32_t)key_index(L[s]) : -1;
     }
   }
 }
 
 // grid (query tiles * splits, N). part != NULL: (N, P1, splits, K) keys; else dists / idx (N, P1, K).
 template <int NORM, int KB, int Q>
-__global__ void __launch_bounds__(MRK_BLOCK) k_knn(const float* __restrict__ p1, const float* __restrict__ p2, int64_t P1,
+__global__ void __launch_bounds__(MRN_BLOCK) k_knn(const float* __restrict__ p1, const float* __restrict__ p2, int64_t P1,
                                                    int64_t P2, const int64_t* __restrict__ l1,
                                                    const int64_t* __restrict__ l2, int K, int splits, int64_t per,
                                                    float* __restrict__ dists, int32_t* __restrict__ idx,
                                                    u64* __restrict__ part) {
-  __shared__ float4 sm[MRK_MAXCHUNK];
+  __shared__ float4 sm[MRN_MAXCHUNK];
   const int64_t n = blockIdx.y;
-  const int64_t q0 = ((int64_t)blockIdx.x / splits) * (MRK_BLOCK * Q);
+  const int64_t q0 = ((int64_t)blockIdx.x / splits) * (MRN_BLOCK * Q);
   const int s = (int)((int64_t)blockIdx.x % splits);
   const int64_t lq = cloud_len(l1, n, P1), lt = cloud_len(l2, n, P2);
   const float* __restrict__ q = p1 + 3 * n * P1;
@@ -107,23 +104,15 @@ __global__ void __launch_bounds__(MRK_BLOCK) k_knn(const float* __restrict__ p1,
 
   float qx[Q], qy[Q], qz[Q];
   u64 L[Q][KB];
+  scan_load_queries(q, q0, lq, nullptr, false, qx, qy, qz);
 #pragma unroll
-  for (int k = 0; k < Q; ++k) {
-    const int64_t i = q0 + k * MRK_BLOCK + threadIdx.x;
-    const bool ok = i < lq;
-    qx[k] = ok ? q[3 * i] : 0.0f;
-    qy[k] = ok ? q[3 * i + 1] : 0.0f;
-    qz[k] = ok ? q[3 * i + 2] : 0.0f;
+  for (int k = 0; k < Q; ++k)
 #pragma unroll
     for (int j = 0; j < KB; ++j) L[k][j] = ~0ull;
-  }
-  for (int64_t t0 = tb; t0 < te; t0 += MRK_MAXCHUNK) {
-    const int cnt = (int)((te - t0 < MRK_MAXCHUNK) ? te - t0 : MRK_MAXCHUNK);
+  for (int64_t t0 = tb; t0 < te; t0 += MRN_MAXCHUNK) {
+    const int cnt = (int)((te - t0 < MRN_MAXCHUNK) ? te - t0 : MRN_MAXCHUNK);
     if (t0 != tb) __syncthreads();  // the previous chunk has been read
-    for (int j = threadIdx.x; j < cnt; j += MRK_BLOCK) {
-      const float* p = t + 3 * (t0 + j);
-      sm[j] = make_float4(p[0], p[1], p[2], 0.0f);
-    }
+    scan_stage(sm, t, t0, cnt, nullptr, false);
     __syncthreads();
     const uint32_t base = (uint32_t)t0;
 #pragma unroll 2
@@ -131,15 +120,14 @@ __global__ void __launch_bounds__(MRK_BLOCK) k_knn(const float* __restrict__ p1,
       const float4 p = sm[j];
 #pragma unroll
       for (int k = 0; k < Q; ++k) {
-        // a distance is >= +0: its bits order as an unsigned integer, below the all-ones of an empty slot
-        const uint32_t b = __float_as_uint(dist3<NORM>(qx[k], qy[k], qz[k], p));
-        if (b < (uint32_t)(L[k][KB - 1] >> 32)) knn_insert<KB>(L[k], ((u64)b << 32) | (u64)(base + (uint32_t)j));
+        const float dd = dist3<NORM>(qx[k], qy[k], qz[k], p);
+        if (__float_as_uint(dd) < key_bits(L[k][KB - 1])) knn_insert<KB>(L[k], nn_key(dd, base + (uint32_t)j));
       }
     }
   }
 #pragma unroll
   for (int k = 0; k < Q; ++k) {
-    const int64_t i = q0 + k * MRK_BLOCK + threadIdx.x;
+    const int64_t i = q0 + k * MRN_BLOCK + threadIdx.x;
     if (i >= P1) continue;
     const int64_t row = n * P1 + i;
     if (part) {
@@ -219,11 +207,9 @@ __global__ void __launch_bounds__(MRK_TBLOCK) k_knn_bwd_p2(const u64* __restrict
 
 int check_knn(const char* who, const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2, int32_t norm,
               int32_t K) {
-  if (N < 1 || P1 < 1 || P2 < 1) return set_err(MR_EINVAL, "%s: N, P1 and P2 must be >= 1", who);
+  if (int rc = check_sizes(who, N, P1, P2)) return rc;
   if (K < 1) return set_err(MR_EINVAL, "%s: K must be >= 1", who);
   if (K > MRK_MAXK) return set_err(MR_EUNSUPPORTED, "%s: K > %d is not built", who, MRK_MAXK);
-  if (!sizes_ok(N, P1, P2))
-    return set_err(MR_EUNSUPPORTED, "%s: more than 65535 clouds or clouds too large for 32-bit point ids", who);
   if (norm != 1 && norm != 2) return set_err(MR_EINVAL, "%s: norm must be 1 or 2", who);
   if (!p1 || !p2) return set_err(MR_EINVAL, "%s: p1 / p2 is NULL", who);
   return MR_OK;
@@ -241,10 +227,9 @@ int32_t mr_knn_geometry(int64_t N, int64_t P1, int64_t P2, int32_t K, int32_t* q
                         int32_t* lds_chunk) {
   if (N < 1 || P1 < 1 || P2 < 1 || K < 1) return set_err(MR_EINVAL, "knn geometry: N, P1, P2 and K must be >= 1");
   if (K > MRK_MAXK) return set_err(MR_EUNSUPPORTED, "knn geometry: K > %d is not built", MRK_MAXK);
-  if (!sizes_ok(N, P1, P2))
-    return set_err(MR_EUNSUPPORTED, "knn geometry: more than 65535 clouds or clouds too large for 32-bit point ids");
+  if (int rc = check_sizes("knn geometry", N, P1, P2)) return rc;
   const KnnGeom g = knn_geom(N, P1, P2, K);
-  if (queries_per_group) *queries_per_group = MRK_BLOCK * g.q;
+  if (queries_per_group) *queries_per_group = MRN_BLOCK * g.q;
   if (splits) *splits = g.splits;
   if (lds_chunk) *lds_chunk = g.chunk;
   return MR_OK;
@@ -270,7 +255,7 @@ int32_t mr_knn_points(const float* p1, const float* p2, int64_t N, int64_t P1, i
   const int k = K, splits = g.splits;
   int rc;
 #define MRK_SCAN(NORM, KB, Q)                                                                                         \
-  rc = launch(KID_NONE, "k_knn", k_knn<NORM, KB, Q>, grid, MRK_BLOCK, 0, st, p1, p2, P1, P2, lengths1, lengths2, k, splits, \
+  rc = launch(KID_NONE, "k_knn", k_knn<NORM, KB, Q>, grid, MRN_BLOCK, 0, st, p1, p2, P1, P2, lengths1, lengths2, k, splits, \
               g.per, dists, idx, part)
 #define MRK_SCAN_K(NORM)            \
   switch (g.kb) {                   \

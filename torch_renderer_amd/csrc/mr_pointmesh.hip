@@ -11,8 +11,8 @@
 //                   (a broadcast) and the record's plane flag is wave-uniform, so a triangle below the area threshold
 //                   costs the three segment terms only. face -> point: a thread keeps one triangle record in
 //                   registers, the chunk holds <= 1024 points as float4. Chunks merge with a 64-bit atomicMin on
-//                   (float bits of dist) << 32 | index within the mesh; the in-chunk comparison is strict, so equal
-//                   distances resolve to the lowest index.
+//                   nn_key (mr_cloud.h) of the distance and the index within the mesh; the in-chunk comparison is
+//                   strict, so equal distances resolve to the lowest index.
 //   k_pm_reduce     keys -> dist / idx per point and per face (0 / -1 without a counterpart), float64 partial sums.
 //   k_pm_final      per mesh: partial sums in order, 1/P_n and 1/T_n, then the batch in a fixed tree and 1/N; leaves
 //                   the backward's coefficients.
@@ -26,6 +26,7 @@
 #include "../../include/mi355r.h"
 #include "mr_common.h"
 #include "mr_host.h"
+#include "mr_cloud.h"
 
 #define MPM_BLOCK 256                    // threads of every kernel here (four waves)
 #define MPM_Q 2                          // points per thread, point -> face
@@ -42,8 +43,6 @@
 #define MPM_EPS 1e-8f                    // upstream's kEpsilon, compared in float32
 
 namespace {
-
-typedef unsigned long long u64;
 
 // A triangle with what pair_dist reuses across queries. plane: 1 the plane branch is open (area >= the
 // threshold and |n| > 1e-8), 0 edges only, -1 not a triangle of the mesh (a vertex id out of range): skipped.
@@ -286,7 +285,7 @@ __global__ void __launch_bounds__(MPM_BLOCK) k_pm_nn(PMBatch b, PMGeom g, u64* _
     for (int k = 0; k < MPM_Q; ++k) {
       const int64_t i = q0 + k * MPM_BLOCK + threadIdx.x;
       if (i < lq && bi[k] >= 0)
-        atomicMin(&key_p[fp + i], ((u64)__float_as_uint(best[k]) << 32) | (u64)(uint32_t)(t0 + bi[k]));
+        atomicMin(&key_p[fp + i], nn_key(best[k], (uint32_t)(t0 + bi[k])));
     }
   } else {
     for (int j = threadIdx.x; j < cnt; j += MPM_BLOCK) {
@@ -310,7 +309,7 @@ __global__ void __launch_bounds__(MPM_BLOCK) k_pm_nn(PMBatch b, PMGeom g, u64* _
         bi = j;
       }
     }
-    if (bi >= 0) atomicMin(&key_f[ff + i], ((u64)__float_as_uint(best) << 32) | (u64)(uint32_t)(t0 + bi));
+    if (bi >= 0) atomicMin(&key_f[ff + i], nn_key(best, (uint32_t)(t0 + bi)));
   }
 }
 
@@ -336,9 +335,9 @@ __global__ void __launch_bounds__(MPM_BLOCK) k_pm_reduce(PMBatch b, const u64* _
     if (i >= lq) continue;
     const u64 kk = key[fq + i];
     const bool ok = kk != ~0ull;
-    const float dv = ok ? __uint_as_float((uint32_t)(kk >> 32)) : 0.0f;
+    const float dv = ok ? key_dist(kk) : 0.0f;
     if (dist) dist[fq + i] = dv;
-    if (idx) idx[fq + i] = ok ? (int32_t)(uint32_t)kk : -1;
+    if (idx) idx[fq + i] = ok ? (int32_t)key_index(kk) : -1;
     s += (double)dv;
   }
   if (part) {  // uniform

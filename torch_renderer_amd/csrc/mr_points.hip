@@ -3,14 +3,12 @@
 // mr_sample_points_* / mr_face_areas of include/mi355r.h. A translation unit of its own (the render kernels of
 // mr_raster.hip and the priors of mr_priors.hip are compiled as before).
 //
-//   k_nn            both directions (x -> y, y -> x) of a batch in one launch. A workgroup of 128 threads takes
-//                   512 queries (4 per thread, in registers) and one chunk of <= 1024 targets staged in LDS as
-//                   float4; every lane reads the same LDS address (a broadcast), one read feeds 4 distance
-//                   evaluations (44 VALU instructions: the loop is VALU-bound). The target range is split into chunks over workgroups (the host picks the chunk
-//                   so that ~1024 workgroups exist per direction); each thread merges its chunk's minimum with a
-//                   64-bit atomicMin on (float bits of dist) << 32 | target index: non-negative float bits order
-//                   as unsigned integers, the minimum does not depend on arrival order, and equal distances
-//                   resolve to the lowest index. The key buffer is set to all-ones by a memset ahead of the launch.
+//   k_nn            both directions (x -> y, y -> x) of a batch in one launch, over the scan of mr_cloud.h: a
+//                   workgroup takes 512 queries (4 per thread) and one chunk of <= 1024 targets (one LDS read feeds 4
+//                   distance evaluations, 44 VALU instructions: the loop is VALU-bound). The target
+//                   range is split into chunks over workgroups (the host picks the chunk so that ~1024 workgroups
+//                   exist per direction); each thread merges its chunk's minimum into the key buffer (nn_key, set to
+//                   all-ones by a memset ahead of the launch) with a 64-bit atomicMin.
 //                   dist = (dx*dx + dy*dy) + dz*dz or (|dx| + |dy|) + |dz| in float32, no FMA.
 //   k_nn_reduce     keys -> dist (float32) / idx (int32) per point, 0 / -1 for entries past a length or of a cloud
 //                   whose counterpart is empty; per-workgroup partial sums of dist (double, fixed tree).
@@ -38,11 +36,9 @@
 #include "mr_host.h"
 #include "mr_cloud.h"
 
-#define MRN_BLOCK 128                  // threads of a k_nn workgroup (two waves)
 #define MRN_Q 4                        // queries per thread
 #define MRN_QT (MRN_BLOCK * MRN_Q)     // queries per workgroup
-#define MRN_MAXCHUNK 1024              // targets staged per workgroup at most (16 KiB of LDS)
-#define MRN_MINCHUNK 64
+#define MRN_MINCHUNK 64                // targets staged per workgroup at least (at most MRN_MAXCHUNK)
 #define MRN_WANT_GROUPS 1024           // workgroups per direction the chunk size aims for
 #define MRR_BLOCK 256                  // threads of the other kernels
 #define MRR_PER 4                      // points per thread of k_nn_reduce
@@ -95,6 +91,36 @@ PointsWS carve_points(void* base, int64_t N, int64_t P1, int64_t P2) {
   return w;
 }
 
+// A workgroup's share of a chunked search: workgroup `group` of a cloud takes query tile group / nchunk and target
+// chunk group % nchunk, and merges each query's nearest target of the chunk into key[query].
+template <int NORM>
+__device__ __forceinline__ void nn_chunk_search(float4* __restrict__ sm, const float* __restrict__ q,
+                                                const float* __restrict__ t, int64_t lq, int64_t lt, int64_t group,
+                                                int64_t nchunk, int chunk, const float* __restrict__ tr, bool apply,
+                                                u64* __restrict__ key) {
+  const int64_t q0 = (group / nchunk) * MRN_QT;
+  const int64_t t0 = (group % nchunk) * chunk;
+  if (q0 >= lq || t0 >= lt) return;  // uniform over the workgroup
+  const int cnt = (int)((lt - t0 < chunk) ? lt - t0 : chunk);
+  scan_stage(sm, t, t0, cnt, nullptr, false);
+  __syncthreads();
+
+  float qx[MRN_Q], qy[MRN_Q], qz[MRN_Q], best[MRN_Q];
+  int bi[MRN_Q];
+  scan_load_queries(q, q0, lq, tr, apply, qx, qy, qz);
+#pragma unroll
+  for (int k = 0; k < MRN_Q; ++k) {
+    best[k] = __builtin_inff();
+    bi[k] = 0;
+  }
+  scan_nearest<NORM>(sm, cnt, 0, qx, qy, qz, best, bi);
+#pragma unroll
+  for (int k = 0; k < MRN_Q; ++k) {
+    const int64_t i = q0 + k * MRN_BLOCK + threadIdx.x;
+    if (i < lq) atomicMin(&key[i], nn_key(best[k], (uint32_t)(t0 + bi[k])));
+  }
+}
+
 template <int NORM>
 __global__ void __launch_bounds__(MRN_BLOCK) k_nn(const float* __restrict__ x, const float* __restrict__ y, NNGeom g,
                                                   const int64_t* __restrict__ xl, const int64_t* __restrict__ yl,
@@ -104,49 +130,9 @@ __global__ void __launch_bounds__(MRN_BLOCK) k_nn(const float* __restrict__ x, c
   if ((int64_t)blockIdx.x >= g.groups[d]) return;
   const int64_t n = blockIdx.y;
   const int64_t Pq = g.P[d], Pt = g.P[1 - d];
-  const float* __restrict__ q = (d ? y : x) + 3 * n * Pq;
-  const float* __restrict__ t = (d ? x : y) + 3 * n * Pt;
-  const int64_t lq = cloud_len(d ? yl : xl, n, Pq), lt = cloud_len(d ? xl : yl, n, Pt);
-  const int64_t q0 = ((int64_t)blockIdx.x / g.nchunk[d]) * MRN_QT;
-  const int64_t t0 = ((int64_t)blockIdx.x % g.nchunk[d]) * g.chunk[d];
-  if (q0 >= lq || t0 >= lt) return;  // uniform over the workgroup
-  const int cnt = (int)((lt - t0 < g.chunk[d]) ? lt - t0 : g.chunk[d]);
-  for (int j = threadIdx.x; j < cnt; j += MRN_BLOCK) {
-    const float* p = t + 3 * (t0 + j);
-    sm[j] = make_float4(p[0], p[1], p[2], 0.0f);
-  }
-  __syncthreads();
-
-  float qx[MRN_Q], qy[MRN_Q], qz[MRN_Q], best[MRN_Q];
-  int bi[MRN_Q];
-#pragma unroll
-  for (int k = 0; k < MRN_Q; ++k) {
-    const int64_t i = q0 + k * MRN_BLOCK + threadIdx.x;
-    const bool ok = i < lq;
-    qx[k] = ok ? q[3 * i] : 0.0f;
-    qy[k] = ok ? q[3 * i + 1] : 0.0f;
-    qz[k] = ok ? q[3 * i + 2] : 0.0f;
-    best[k] = __builtin_inff();
-    bi[k] = 0;
-  }
-#pragma unroll 4
-  for (int j = 0; j < cnt; ++j) {
-    const float4 p = sm[j];
-#pragma unroll
-    for (int k = 0; k < MRN_Q; ++k) {
-      const float dd = dist3<NORM>(qx[k], qy[k], qz[k], p);
-      if (dd < best[k]) {  // strict: the lowest index wins a tie inside the chunk
-        best[k] = dd;
-        bi[k] = j;
-      }
-    }
-  }
-  u64* __restrict__ key = (d ? key_y : key_x) + n * Pq;
-#pragma unroll
-  for (int k = 0; k < MRN_Q; ++k) {
-    const int64_t i = q0 + k * MRN_BLOCK + threadIdx.x;
-    if (i < lq) atomicMin(&key[i], ((u64)__float_as_uint(best[k]) << 32) | (u64)(uint32_t)(t0 + bi[k]));
-  }
+  nn_chunk_search<NORM>(sm, (d ? y : x) + 3 * n * Pq, (d ? x : y) + 3 * n * Pt, cloud_len(d ? yl : xl, n, Pq),
+                        cloud_len(d ? xl : yl, n, Pt), blockIdx.x, g.nchunk[d], g.chunk[d], nullptr, false,
+                        (d ? key_y : key_x) + n * Pq);
 }
 
 // grid (nblk, N, directions). dist / idx / part may each be NULL.
@@ -171,9 +157,9 @@ __global__ void __launch_bounds__(MRR_BLOCK) k_nn_reduce(NNGeom g, const int64_t
     if (i >= Pq) continue;
     const bool ok = i < lq && lt > 0;
     const u64 kk = ok ? key[i] : 0;
-    const float dv = ok ? __uint_as_float((uint32_t)(kk >> 32)) : 0.0f;
+    const float dv = ok ? key_dist(kk) : 0.0f;
     if (dist) dist[n * Pq + i] = dv;
-    if (idx) idx[n * Pq + i] = ok ? (int32_t)(uint32_t)kk : -1;
+    if (idx) idx[n * Pq + i] = ok ? (int32_t)key_index(kk) : -1;
     s += (double)dv;
   }
   if (part) {  // uniform
@@ -366,9 +352,7 @@ __global__ void __launch_bounds__(MRR_BLOCK) k_face_areas(const float* __restric
 }
 
 int check_clouds(const char* who, const float* x, const float* y, int64_t N, int64_t P1, int64_t P2, int32_t norm) {
-  if (N < 1 || P1 < 1 || P2 < 1) return set_err(MR_EINVAL, "%s: N, P1 and P2 must be >= 1", who);
-  if (!sizes_ok(N, P1, P2))
-    return set_err(MR_EUNSUPPORTED, "%s: more than 65535 clouds or clouds too large for 32-bit point ids", who);
+  if (int rc = check_sizes(who, N, P1, P2)) return rc;
   if (norm != 1 && norm != 2) return set_err(MR_EINVAL, "%s: norm must be 1 or 2", who);
   if (!x || !y) return set_err(MR_EINVAL, "%s: x / y is NULL", who);
   return MR_OK;
@@ -391,7 +375,7 @@ bool mesh_sizes_ok(int64_t V, int64_t F, int64_t M) {
 
 // ---------------------------------------------------------------------------
 // Similarity alignment and ICP (PyTorch3D corresponding_points_alignment / iterative_closest_point).
-// A cloud's transform is 13 floats, R (3x3 row-major), T (3), s: y = s (x R) + T with row vectors.
+// A cloud's transform is the 13 floats of sim_apply (mr_cloud.h).
 // ---------------------------------------------------------------------------
 #define MRI_RTS 13
 #define MRI_XC 8        // per-cloud constants (double): sum w, mean of x (3), sum w |x - mean|^2, sum w (x - mean) (3)
@@ -427,17 +411,9 @@ IcpWS carve_icp(void* base, int64_t N, int64_t P1) {
   return w;
 }
 
-// The one transform code: the NN search, the residual and the final points all call it.
-__device__ __forceinline__ void sim_apply(const float* __restrict__ t, float x0, float x1, float x2, float& o0,
-                                          float& o1, float& o2) {
-  const float s = t[12];
-  o0 = s * ((x0 * t[0] + x1 * t[3]) + x2 * t[6]) + t[9];
-  o1 = s * ((x0 * t[1] + x1 * t[4]) + x2 * t[7]) + t[10];
-  o2 = s * ((x0 * t[2] + x1 * t[5]) + x2 * t[8]) + t[11];
-}
-
-// K sums over a 256-thread workgroup, each in block_sum's tree; sm: 4 * K doubles. Every thread gets the totals.
-template <int K> __device__ __forceinline__ void block_sums(double (&v)[K], double* sm) {
+// K sums over a workgroup of WAVES waves: the butterfly inside each wave, then wave 0 + wave 1 (+ wave 2 + wave 3,
+// block_sum's tree). sm: WAVES * K doubles. Every thread gets the totals.
+template <int WAVES, int K> __device__ __forceinline__ void block_sums(double (&v)[K], double* sm) {
 #pragma unroll
   for (int k = 0; k < K; ++k)
     for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
@@ -447,7 +423,11 @@ template <int K> __device__ __forceinline__ void block_sums(double (&v)[K], doub
   }
   __syncthreads();
 #pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = ((sm[k] + sm[K + k]) + sm[2 * K + k]) + sm[3 * K + k];
+  for (int k = 0; k < K; ++k) {
+    v[k] = sm[k];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) v[k] += sm[w * K + k];
+  }
   __syncthreads();
 }
 
@@ -482,7 +462,7 @@ __global__ void __launch_bounds__(MRR_BLOCK) k_icp_xstats(const float* __restric
     a[2] += w * (double)q[3 * i + 1];
     a[3] += w * (double)q[3 * i + 2];
   }
-  block_sums<4>(a, sm);
+  block_sums<MRR_BLOCK / 64>(a, sm);
   const double wc = a[0] > eps ? a[0] : eps;
   const double m0 = a[1] / wc, m1 = a[2] / wc, m2 = a[3] / wc;
   double b[4] = {0.0, 0.0, 0.0, 0.0};
@@ -494,7 +474,7 @@ __global__ void __launch_bounds__(MRR_BLOCK) k_icp_xstats(const float* __restric
     b[2] += w * d1;
     b[3] += w * d2;
   }
-  block_sums<4>(b, sm);
+  block_sums<MRR_BLOCK / 64>(b, sm);
   if (threadIdx.x == 0) {
     double* o = xc + n * MRI_XC;
     o[0] = a[0];
@@ -527,48 +507,8 @@ __global__ void __launch_bounds__(MRN_BLOCK) k_icp_nn(const float* __restrict__ 
   if ((int64_t)blockIdx.x >= g.groups[0]) return;
   const int64_t n = blockIdx.y;
   const int64_t Pq = g.P[0], Pt = g.P[1];
-  const float* __restrict__ q = x + 3 * n * Pq;
-  const float* __restrict__ t = y + 3 * n * Pt;
-  const int64_t lq = cloud_len(xl, n, Pq), lt = cloud_len(yl, n, Pt);
-  const int64_t q0 = ((int64_t)blockIdx.x / g.nchunk[0]) * MRN_QT;
-  const int64_t t0 = ((int64_t)blockIdx.x % g.nchunk[0]) * g.chunk[0];
-  if (q0 >= lq || t0 >= lt) return;  // uniform over the workgroup
-  const int cnt = (int)((lt - t0 < g.chunk[0]) ? lt - t0 : g.chunk[0]);
-  for (int j = threadIdx.x; j < cnt; j += MRN_BLOCK) {
-    const float* p = t + 3 * (t0 + j);
-    sm[j] = make_float4(p[0], p[1], p[2], 0.0f);
-  }
-  __syncthreads();
-
-  const float* __restrict__ tr = rts + n * MRI_RTS;
-  float qx[MRN_Q], qy[MRN_Q], qz[MRN_Q], best[MRN_Q];
-  int bi[MRN_Q];
-#pragma unroll
-  for (int k = 0; k < MRN_Q; ++k) {
-    const int64_t i = q0 + k * MRN_BLOCK + threadIdx.x;
-    const bool ok = i < lq;
-    sim_apply(tr, ok ? q[3 * i] : 0.0f, ok ? q[3 * i + 1] : 0.0f, ok ? q[3 * i + 2] : 0.0f, qx[k], qy[k], qz[k]);
-    best[k] = __builtin_inff();
-    bi[k] = 0;
-  }
-#pragma unroll 4
-  for (int j = 0; j < cnt; ++j) {
-    const float4 p = sm[j];
-#pragma unroll
-    for (int k = 0; k < MRN_Q; ++k) {
-      const float dd = dist3<2>(qx[k], qy[k], qz[k], p);
-      if (dd < best[k]) {  // strict: the lowest index wins a tie inside the chunk
-        best[k] = dd;
-        bi[k] = j;
-      }
-    }
-  }
-  u64* __restrict__ key = key_x + n * Pq;
-#pragma unroll
-  for (int k = 0; k < MRN_Q; ++k) {
-    const int64_t i = q0 + k * MRN_BLOCK + threadIdx.x;
-    if (i < lq) atomicMin(&key[i], ((u64)__float_as_uint(best[k]) << 32) | (u64)(uint32_t)(t0 + bi[k]));
-  }
+  nn_chunk_search<2>(sm, x + 3 * n * Pq, y + 3 * n * Pt, cloud_len(xl, n, Pq), cloud_len(yl, n, Pt), blockIdx.x,
+                     g.nchunk[0], g.chunk[0], rts + n * MRI_RTS, true, key_x + n * Pq);
 }
 
 // grid (nblk, N): the moments of a tile of source points against their correspondences. key != NULL: the
@@ -599,7 +539,7 @@ __global__ void __launch_bounds__(MRR_BLOCK) k_icp_moments(const float* __restri
       if (key) {
         const u64 kk = key[n * P1 + i];
         key[n * P1 + i] = ~0ull;
-        j = (int64_t)(uint32_t)kk;
+        j = (int64_t)key_index(kk);
       } else {
         j = i;
       }
@@ -625,7 +565,7 @@ __global__ void __launch_bounds__(MRR_BLOCK) k_icp_moments(const float* __restri
     a[10] += d2 * y1;
     a[11] += d2 * y2;
   }
-  block_sums<MRI_MOM>(a, sm);
+  block_sums<MRR_BLOCK / 64>(a, sm);
   if (threadIdx.x < MRI_MOM) {
     double v = 0.0;
 #pragma unroll
@@ -852,22 +792,6 @@ PosedWS carve_posed(void* base, int64_t S, int64_t P1, int64_t P2) {
   return w;
 }
 
-// block_sums for a k_nn-sized workgroup (MRN_BLOCK = 128 threads, two waves): the butterfly inside each wave, then
-// wave 0 + wave 1. sm: 2 * K doubles. Every thread gets the totals.
-template <int K> __device__ __forceinline__ void tile_sums(double (&v)[K], double* sm) {
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) sm[(threadIdx.x >> 6) * K + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = sm[k] + sm[K + k];
-  __syncthreads();
-}
-
 // grid (query tiles of the larger cloud, S, directions). A workgroup owns one pose, one direction and one tile of
 // 512 queries and scans ALL targets itself, in ascending LDS chunks: with the strict < its minimum is final and
 // ties go to the lowest index, so there is no key buffer, memset, atomic or decode pass. Direction 0: queries x'
@@ -875,12 +799,14 @@ template <int K> __device__ __forceinline__ void tile_sums(double (&v)[K], doubl
 // are staged: the same sim_apply, so both directions see the bits a materialised cloud would hold. Outputs per
 // workgroup: idx (optional), the float64 sum of its queries' distances, and (mom != NULL) the pose moments with
 // g = x' - y of every pair (sign(.) for norm 1) and x the pair's untransformed source point.
+// Norm 2 is held at the 4 waves per SIMD it has always run at (97-128 VGPRs; 8 workgroups = 16 waves per CU, 4 on
+// every SIMD). At <= 96 VGPRs the LDS admits a ninth workgroup, whose 2 waves load the four SIMDs 5, 5, 4, 4, and
+// the VALU-bound scan ran 11 % slower at S = 1000, P = 1000 / 495 (profiles/nn_scan_ab.json). Norm 1 is as it was.
 template <int NORM>
-__global__ void __launch_bounds__(MRN_BLOCK) k_posed_nn(const float* __restrict__ x, const float* __restrict__ y,
-                                                        int64_t P1, int64_t P2, const float* __restrict__ rts,
-                                                        int64_t S, int64_t ntile, int32_t* __restrict__ idx_x,
-                                                        int32_t* __restrict__ idx_y, double* __restrict__ part,
-                                                        double* __restrict__ mom) {
+__global__ void __launch_bounds__(MRN_BLOCK) __attribute__((amdgpu_waves_per_eu(4, NORM == 2 ? 4 : 8))) k_posed_nn(
+    const float* __restrict__ x, const float* __restrict__ y, int64_t P1, int64_t P2, const float* __restrict__ rts,
+    int64_t S, int64_t ntile, int32_t* __restrict__ idx_x, int32_t* __restrict__ idx_y, double* __restrict__ part,
+    double* __restrict__ mom) {
   __shared__ float4 sm[MRN_MAXCHUNK];
   __shared__ double red[2 * MRP_MOM];
   const int d = blockIdx.z;
@@ -894,44 +820,18 @@ __global__ void __launch_bounds__(MRN_BLOCK) k_posed_nn(const float* __restrict_
 
   float qx[MRN_Q], qy[MRN_Q], qz[MRN_Q], best[MRN_Q];
   int bi[MRN_Q];
+  scan_load_queries(q, q0, Pq, tr, d == 0, qx, qy, qz);
 #pragma unroll
   for (int k = 0; k < MRN_Q; ++k) {
-    const int64_t i = q0 + k * MRN_BLOCK + threadIdx.x;
-    const bool ok = i < Pq;
-    const float a0 = ok ? q[3 * i] : 0.0f, a1 = ok ? q[3 * i + 1] : 0.0f, a2 = ok ? q[3 * i + 2] : 0.0f;
-    if (d == 0) {
-      sim_apply(tr, a0, a1, a2, qx[k], qy[k], qz[k]);
-    } else {
-      qx[k] = a0;
-      qy[k] = a1;
-      qz[k] = a2;
-    }
     best[k] = __builtin_inff();
     bi[k] = 0;
   }
   for (int64_t t0 = 0; t0 < Pt; t0 += MRN_MAXCHUNK) {
     const int cnt = (int)((Pt - t0 < MRN_MAXCHUNK) ? Pt - t0 : MRN_MAXCHUNK);
     if (t0) __syncthreads();  // the previous chunk has been read
-    for (int j = threadIdx.x; j < cnt; j += MRN_BLOCK) {
-      const float* p = t + 3 * (t0 + j);
-      float p0 = p[0], p1 = p[1], p2 = p[2];
-      if (d) sim_apply(tr, p0, p1, p2, p0, p1, p2);
-      sm[j] = make_float4(p0, p1, p2, 0.0f);
-    }
+    scan_stage(sm, t, t0, cnt, tr, d != 0);
     __syncthreads();
-    const int base = (int)t0;
-#pragma unroll 4
-    for (int j = 0; j < cnt; ++j) {
-      const float4 p = sm[j];
-#pragma unroll
-      for (int k = 0; k < MRN_Q; ++k) {
-        const float dd = dist3<NORM>(qx[k], qy[k], qz[k], p);
-        if (dd < best[k]) {  // strict, ascending chunks: the lowest index wins a tie
-          best[k] = dd;
-          bi[k] = base + j;
-        }
-      }
-    }
+    scan_nearest<NORM>(sm, cnt, (int)t0, qx, qy, qz, best, bi);
   }
 
   int32_t* __restrict__ idx = d ? idx_y : idx_x;
@@ -989,11 +889,11 @@ __global__ void __launch_bounds__(MRN_BLOCK) k_posed_nn(const float* __restrict_
   const int64_t slot = ((int64_t)d * S + n) * ntile + blockIdx.x;
   {
     double one[1] = {dsum};
-    tile_sums<1>(one, red);
+    block_sums<MRN_BLOCK / 64>(one, red);
     if (threadIdx.x == 0) part[slot] = one[0];
   }
   if (!mom) return;  // uniform
-  tile_sums<MRP_MOM>(a, red);
+  block_sums<MRN_BLOCK / 64>(a, red);
   if (threadIdx.x < MRP_MOM) {
     double v = 0.0;
 #pragma unroll
@@ -1198,9 +1098,7 @@ size_t mr_icp_workspace(int64_t N, int64_t P1, int64_t P2) {
 }
 
 static int check_icp(const char* who, const float* x, int64_t N, int64_t P1, int64_t P2) {
-  if (N < 1 || P1 < 1 || P2 < 1) return set_err(MR_EINVAL, "%s: N, P1 and P2 must be >= 1", who);
-  if (!sizes_ok(N, P1, P2))
-    return set_err(MR_EUNSUPPORTED, "%s: more than 65535 clouds or clouds too large for 32-bit point ids", who);
+  if (int rc = check_sizes(who, N, P1, P2)) return rc;
   if (!x) return set_err(MR_EINVAL, "%s: x is NULL", who);
   return MR_OK;
 }
