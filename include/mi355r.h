@@ -702,6 +702,36 @@ int32_t mr_farthest_points(const float* points, int64_t N, int64_t P, const int6
                            int64_t Kmax, const int64_t* start_idx, int32_t* idx, float* pts, void* ws, size_t ws_bytes,
                            void* stream);
 
+/* Local coordinate frames of point clouds (PyTorch3D estimate_pointcloud_local_coord_frames; column 0 of a frame is
+ * estimate_pointcloud_normals), 2 <= K <= 64 (MR_EINVAL below, MR_EUNSUPPORTED above). For point i < L = lengths[n]
+ * (NULL: P; clamped to [0, P]) of points (N,P,3): the neighbourhood is the K smallest (distance, index) pairs over the
+ * same cloud, the point itself included, with mr_knn_points' float32 squared distance and tie rule. With
+ * d_k = p_k - p_i and m = mean_k d_k, C = (1/K) sum_k (d_k - m)(d_k - m)^T in float32, summed in neighbour order.
+ * curvatures (N,P,3) are C's eigenvalues ascending, frames (N,P,3,3) holds in frames[n,i,:,j] the unit eigenvector of
+ * the j-th (column 0 the normal, column 2 the main direction), cov (N,P,6; may be NULL) the upper triangle of C as
+ * xx, xy, xz, yy, yz, zz. The solve is a fixed-sweep cyclic Jacobi in float32 on C / trace(C): the frames do not
+ * depend on the cloud's scale. C = 0 gives curvatures 0 and the identity before the sign step.
+ * Signs: with MR_FRAMES_DISAMBIGUATE, columns 0 and 2 are negated iff 2 #{k : (v_x d_kx + v_y d_ky) + v_z d_kz > 0} < K
+ * and column 1 becomes cross(column 0, column 2); without, every column's component of largest magnitude is made
+ * positive (the lowest axis among equal magnitudes).
+ * Rows i >= L, and every row of a cloud with L < K, are zeros in all outputs. P <= K is MR_EINVAL.
+ * One launch whose threads each scan their cloud for their queries' neighbours (lists in registers, bucket 8, 16, 32
+ * or 64) and solve in place; only when N * query tiles < 256 is the target range cut into <= 16 splits whose sorted
+ * partial lists go through the workspace (8 K splits bytes per point) to a launch that merges and solves. The result
+ * does not depend on the splits. No memset, no atomics; bitwise reproducible. mr_point_frames_geometry (host only)
+ * returns what the launch would use: the bucket, queries per workgroup, splits, and the targets staged in LDS at a
+ * time (each pointer may be NULL). All arguments are checked before any GPU call.
+ *
+ * mr_symmetric_eig3_host (host only, no GPU): the same solver over M symmetric 3x3 matrices given as (M,6) upper
+ * triangles; eigenvalues (M,3) ascending, eigenvectors (M,3,3) in columns, signed as without MR_FRAMES_DISAMBIGUATE. */
+enum { MR_FRAMES_DISAMBIGUATE = 1 };
+int32_t mr_point_frames_geometry(int64_t N, int64_t P, int32_t K, int32_t* bucket, int32_t* queries_per_group,
+                                 int32_t* splits, int32_t* lds_chunk);
+size_t mr_point_frames_workspace(int64_t N, int64_t P, int32_t K);
+int32_t mr_point_frames(const float* points, int64_t N, int64_t P, const int64_t* lengths, int32_t K, int32_t flags,
+                        float* curvatures, float* frames, float* cov, void* ws, size_t ws_bytes, void* stream);
+int32_t mr_symmetric_eig3_host(const float* cov, int64_t M, float* eigenvalues, float* eigenvectors);
+
 /* Per-kernel timing with HIP events recorded on each launch's stream (bench.py).
  * enable=1 clears and starts collection; mr_timing_read synchronizes on the
  * recorded events and returns, per kernel id, launches and summed ms. */

@@ -33,6 +33,7 @@ MR_PRIOR_EDGE, MR_PRIOR_LAPLACIAN, MR_PRIOR_NORMAL, MR_PRIOR_ALL = 1, 2, 4, 7  #
 MR_CHAMFER_POINT_MEAN, MR_CHAMFER_BATCH_MEAN, MR_CHAMFER_BATCH_SUM, MR_CHAMFER_SINGLE = 1, 2, 4, 8  # mr_chamfer_*: flags
 MR_ICP_ESTIMATE_SCALE, MR_ICP_ALLOW_REFLECTION = 1, 2  # mr_icp_iterate / mr_points_alignment: flags
 MR_COMPOSITE_NORM, MR_COMPOSITE_DISTS = 1, 2  # mr_composite_points_*: flags
+MR_FRAMES_DISAMBIGUATE = 1  # mr_point_frames: flags
 
 
 class MrView(ctypes.Structure):
@@ -179,6 +180,10 @@ _SIGS = [
     ("mr_farthest_points_geometry", _I32, [_I64, _I64, _I64, c_i32_p, c_i32_p, c_i32_p]),
     ("mr_farthest_points_workspace", _SZ, [_I64, _I64, _I64]),
     ("mr_farthest_points", _I32, [_VP, _I64, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    ("mr_point_frames_geometry", _I32, [_I64, _I64, _I32, c_i32_p, c_i32_p, c_i32_p, c_i32_p]),
+    ("mr_point_frames_workspace", _SZ, [_I64, _I64, _I32]),
+    ("mr_point_frames", _I32, [_VP, _I64, _I64, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    ("mr_symmetric_eig3_host", _I32, [_VP, _I64, _VP, _VP]),
     ("mr_icp_workspace", _SZ, [_I64, _I64, _I64]),
     ("mr_icp_init", _I32, [_VP, _I64, _I64, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     ("mr_icp_iterate", _I32, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, _I32, ctypes.c_float, _I32, _I32, _VP, _VP, _VP,

@@ -16,6 +16,7 @@
 //   k_knn_bwd     one thread per query: grad_p1 = sum_k 2 g (p1 - p2[idx]) (norm 1: g sign(.)) with a plain store, and
 //                 the same addends into the targets' rows with 64-bit fixed-point integer atomics (mr_common.h);
 //   k_knn_bwd_p2  grad_p2 = -(row). Slots with idx < 0 contribute nothing and their g is not read.
+// The geometry (knn_geom), the split constants and knn_insert are mr_knn.h's, shared with mr_normals.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -23,52 +24,11 @@
 #include "mr_common.h"
 #include "mr_host.h"
 #include "mr_cloud.h"
+#include "mr_knn.h"
 
 #define MRK_MAXK 32
-#define MRK_MAXSPLIT 16
-#define MRK_CUS 256            // fewer (cloud, query tile) pairs than this: the target range is split
-#define MRK_WANT_GROUPS 1024   // workgroups a split launch aims for
-#define MRK_SPLIT_ALIGN 64     // a split's targets are a multiple of this
-#define MRK_TBLOCK 256         // threads of the per-query kernels
 
 namespace {
-
-struct KnnGeom {
-  int kb, q;        // the bucket of K; queries per thread
-  int64_t qtiles;   // query tiles per cloud
-  int splits;
-  int64_t per;      // targets per split
-  int chunk;        // targets staged at a time
-};
-
-KnnGeom knn_geom(int64_t N, int64_t P1, int64_t P2, int K) {
-  KnnGeom g;
-  g.kb = 1;
-  while (g.kb < K) g.kb *= 2;
-  g.q = g.kb <= 8 ? 4 : (g.kb == 16 ? 2 : 1);
-  g.qtiles = (P1 + MRN_BLOCK * g.q - 1) / (MRN_BLOCK * g.q);
-  g.splits = 1;
-  g.per = P2;
-  const int64_t groups = N * g.qtiles;
-  if (groups < MRK_CUS) {
-    int64_t want = (MRK_WANT_GROUPS + groups - 1) / groups;
-    if (want > MRK_MAXSPLIT) want = MRK_MAXSPLIT;
-    g.per = ((P2 + want - 1) / want + MRK_SPLIT_ALIGN - 1) / MRK_SPLIT_ALIGN * MRK_SPLIT_ALIGN;
-    g.splits = (int)((P2 + g.per - 1) / g.per);
-  }
-  g.chunk = (int)(g.per < MRN_MAXCHUNK ? g.per : MRN_MAXCHUNK);
-  return g;
-}
-
-// c < L[KB - 1] is known: c takes its place in the ascending list and the worst key leaves. Compile-time indices only.
-template <int KB> __device__ __forceinline__ void knn_insert(u64 (&L)[KB], u64 c) {
-#pragma unroll
-  for (int i = KB - 1; i > 0; --i) {
-    const u64 below = L[i - 1];
-    L[i] = c < below ? below : (c < L[i] ? c : L[i]);
-  }
-  L[0] = c < L[0] ? c : L[0];
-}
 
 // The first K slots of a list as dists / idx: 0 / -1 for a slot that was never filled (or a row past its length).
 template <int KB>
@@ -213,10 +173,6 @@ int check_knn(const char* who, const float* p1, const float* p2, int64_t N, int6
   if (norm != 1 && norm != 2) return set_err(MR_EINVAL, "%s: norm must be 1 or 2", who);
   if (!p1 || !p2) return set_err(MR_EINVAL, "%s: p1 / p2 is NULL", who);
   return MR_OK;
-}
-
-size_t knn_part_bytes(int64_t N, int64_t P1, int K, const KnnGeom& g) {
-  return g.splits > 1 ? sizeof(u64) * (size_t)(N * P1) * (size_t)K * (size_t)g.splits : 0;
 }
 
 }  // namespace

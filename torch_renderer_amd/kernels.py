@@ -476,6 +476,75 @@ class FarthestPoints(torch.autograd.Function):
         return grad, None, None, None, None
 
 
+# --------------------------------------------------------------------------- local frames (csrc/mr_normals.hip)
+FRAMES_MIN_K, FRAMES_MAX_K = 2, 64
+
+
+def _frames_k(K, P):
+    K = int(K)
+    if K < FRAMES_MIN_K:
+        raise ValueError(f"point frames: the neighbourhood size must be >= {FRAMES_MIN_K}")
+    if K > FRAMES_MAX_K:
+        raise NotImplementedError(f"point frames: a neighbourhood size > {FRAMES_MAX_K} is not built")
+    if P <= K:
+        raise ValueError("The neighborhood_size argument has to be smaller than the number of points in each "
+                         f"pointcloud (P = {P}, neighbourhood size {K}).")
+    return K
+
+
+def frames_geometry(N, P, K):
+    """(bucket, queries_per_group, splits, lds_chunk) of the launch mr_point_frames makes for these shapes (host only)."""
+    out = [ctypes.c_int32() for _ in range(4)]
+    check(_lib.load().mr_point_frames_geometry(int(N), int(P), _frames_k(K, int(P)), *(ctypes.byref(o) for o in out)))
+    return tuple(o.value for o in out)
+
+
+def symmetric_eig3_host(cov):
+    """(eigenvalues (M,3) ascending, eigenvectors (M,3,3) in columns) of M symmetric 3x3 matrices given as an (M,6)
+    float32 CPU tensor of upper triangles xx, xy, xz, yy, yz, zz: the solver of mr_point_frames run on the host
+    (mr_symmetric_eig3_host; no GPU). Every column's component of largest magnitude is positive."""
+    if cov.dim() != 2 or cov.shape[1] != 6 or cov.dtype != torch.float32 or cov.device.type != "cpu":
+        raise ValueError("symmetric_eig3_host: cov must be an (M, 6) float32 CPU tensor")
+    cov = cov.contiguous()
+    M = cov.shape[0]
+    lam, vec = torch.empty((M, 3)), torch.empty((M, 3, 3))
+    check(_lib.load().mr_symmetric_eig3_host(ptr(cov), M, ptr(lam), ptr(vec)))
+    return lam, vec
+
+
+def point_frames(points, lengths=None, K=50, disambiguate=True, return_cov=False):
+    """(curvatures (N,P,3), frames (N,P,3,3)[, cov (N,P,6)]) in float32, by the rule of mr_point_frames
+    (include/mi355r.h): for every point i < lengths[n] of points (N,P,3), the covariance of its K nearest points of the
+    same cloud (itself included; knn_points' distance and tie rule) about their mean, its eigenvalues ascending and
+    their unit eigenvectors in the columns of the frame (column 0 the normal). ``disambiguate`` signs columns 0 and 2
+    towards the majority of the neighbours and makes column 1 their cross product; otherwise every column's largest
+    component is positive. ``cov`` is the covariance's upper triangle xx, xy, xz, yy, yz, zz. Rows past a length, and
+    every row of a cloud shorter than K, are zeros; P <= K raises ValueError. 2 <= K <= 64. No autograd; one launch,
+    or a scan and a merge when the shapes alone cannot fill the chip; nothing synchronises."""
+    if points.dim() != 3:
+        raise ValueError("point frames: points must be an (N, P, D) tensor")
+    if points.shape[2] != 3:
+        raise ValueError("point frames: the points must be 3-dimensional (D = 3)")
+    N, P = points.shape[0], points.shape[1]
+    if N < 1:
+        raise ValueError("point frames: N must be >= 1")
+    K = _frames_k(K, P)
+    if lengths is not None and tuple(lengths.shape) != (N,):
+        raise ValueError("lengths must be of shape (N,)")
+    _require_cuda(points, lengths)
+    pf = points.detach().float().contiguous()
+    l = None if lengths is None else lengths.detach().to(torch.int64).contiguous()
+    L = _lib.load()
+    dev = pf.device
+    cur, frm = torch.empty((N, P, 3), device=dev), torch.empty((N, P, 3, 3), device=dev)
+    cov = torch.empty((N, P, 6), device=dev) if return_cov else None
+    wsb = _ws_size(L.mr_point_frames_workspace, N, P, K)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    check(L.mr_point_frames(ptr(pf), N, P, ptr(l), K, _lib.MR_FRAMES_DISAMBIGUATE if disambiguate else 0, ptr(cur),
+                            ptr(frm), ptr(cov), ptr(ws), wsb, _lib.stream_handle(dev)))
+    return (cur, frm, cov) if return_cov else (cur, frm)
+
+
 def _one_cloud(t, name):
     """A (P,3) or (1,P,3) cloud as a contiguous float32 (P,3) tensor."""
     if t.dim() == 3 and t.shape[0] == 1:

@@ -15,6 +15,9 @@ k_icp_* kernels of csrc/mr_points.hip). Neither is differentiable.
 
 ``sample_farthest_points`` (csrc/mr_fps.hip): one workgroup per cloud runs all K rounds on the device; the selected
 points are differentiable w.r.t. the input points.
+
+``estimate_pointcloud_normals`` and ``estimate_pointcloud_local_coord_frames`` (csrc/mr_normals.hip): the K <= 64
+neighbourhood scan, the covariance and its 3x3 eigen solve in one launch. Not differentiable.
 """
 from __future__ import annotations
 
@@ -326,3 +329,63 @@ def sample_farthest_points(points, lengths=None, K=50, random_start_point: bool 
             start = torch.minimum((u * span).long(), span.long() - 1)
     pts, idx = kernels.FarthestPoints.apply(points, lengths, K, start, Kmax)
     return pts.to(points.dtype), idx.long()
+
+
+def estimate_pointcloud_local_coord_frames(pointclouds, neighborhood_size: int = 50,
+                                           disambiguate_directions: bool = True, *,
+                                           use_symeig_workaround: bool = True):
+    """``pytorch3d.ops.estimate_pointcloud_local_coord_frames``: (curvatures (N,P,3), local_coord_frames (N,P,3,3)) of
+    an (N,P,3) tensor or a ``Pointclouds``, in the input's dtype (coordinates are read as float32).
+
+    For point i of a cloud of L points, with K = ``neighborhood_size``: the neighbourhood is its K nearest points of
+    the same cloud, itself included (float32 squared distance (dx*dx + dy*dy) + dz*dz, equal distances to the lowest
+    index: ``knn_points(p, p, K=K)``). With d_k = p_k - p_i and m their mean, C = (1/K) sum_k (d_k - m)(d_k - m)^T;
+    ``curvatures[n,i]`` are C's eigenvalues ascending and ``local_coord_frames[n,i,:,j]`` is the unit eigenvector of
+    the j-th: column 0 is the normal, column 2 the main direction. The solve is a fixed-sweep Jacobi in float32 on
+    C / trace(C), so a rescaled cloud gives the same frames; C = 0 (K coincident points) gives zero curvatures and
+    the identity before the signs.
+
+    With ``disambiguate_directions`` columns 0 and 2 are negated iff fewer than half of the d_k have a positive
+    projection on them, and column 1 becomes cross(column 0, column 2). Without, every column's component of largest
+    magnitude is positive, the lowest axis among equal magnitudes (a convention of this library; upstream leaves the
+    sign to ``eigh``). Rows past a cloud's length are zeros. ``use_symeig_workaround`` is accepted and ignored.
+
+    2 <= K <= 64 (``NotImplementedError`` above); a cloud with L <= K, or D != 3, raises ``ValueError``. Not
+    differentiable: an input that requires grad raises ``NotImplementedError`` unless grad mode is off. With a tensor
+    input nothing synchronises and the call captures into a HIP graph; a ``Pointclouds``' lengths are checked on the
+    host. One launch (kernels.point_frames, csrc/mr_normals.hip)."""
+    if isinstance(pointclouds, Pointclouds):
+        counts = pointclouds.counts()
+        points = pointclouds.points_padded()
+        lengths = None if all(c == points.shape[1] for c in counts) else pointclouds.num_points_per_cloud()
+    elif torch.is_tensor(pointclouds):
+        if pointclouds.dim() != 3:
+            raise ValueError("estimate_pointcloud_local_coord_frames: pointclouds must be an (N, P, 3) tensor")
+        points, lengths = pointclouds, None
+        counts = [points.shape[1]] * points.shape[0]
+    else:
+        raise ValueError("estimate_pointcloud_local_coord_frames: pointclouds is an (N, P, 3) tensor or a Pointclouds")
+    if points.shape[2] != 3:
+        raise ValueError("The pointclouds argument has to be of shape (minibatch, N, 3)")
+    K = int(neighborhood_size)
+    if K < kernels.FRAMES_MIN_K:
+        raise ValueError(f"estimate_pointcloud_local_coord_frames: neighborhood_size must be >= {kernels.FRAMES_MIN_K}")
+    if K > kernels.FRAMES_MAX_K:
+        raise NotImplementedError(f"estimate_pointcloud_local_coord_frames: neighborhood_size > {kernels.FRAMES_MAX_K} "
+                                  "is not built")
+    if any(c <= K for c in counts):
+        raise ValueError("The neighborhood_size argument has to be smaller than the size of each of the point clouds.")
+    _refuse_grad("estimate_pointcloud_local_coord_frames", points)
+    _require_cuda(points)
+    cur, frm = kernels.point_frames(points, lengths, K, bool(disambiguate_directions))
+    return cur.to(points.dtype), frm.to(points.dtype)
+
+
+def estimate_pointcloud_normals(pointclouds, neighborhood_size: int = 50, disambiguate_directions: bool = True, *,
+                                use_symeig_workaround: bool = True):
+    """``pytorch3d.ops.estimate_pointcloud_normals``: (N,P,3), column 0 of
+    ``estimate_pointcloud_local_coord_frames`` (the unit eigenvector of the smallest eigenvalue of every point's
+    neighbourhood covariance), with the same arguments, limits and errors."""
+    _, frames = estimate_pointcloud_local_coord_frames(pointclouds, neighborhood_size, disambiguate_directions,
+                                                       use_symeig_workaround=use_symeig_workaround)
+    return frames[..., 0]
