@@ -732,6 +732,37 @@ int32_t mr_point_frames(const float* points, int64_t N, int64_t P, const int64_t
                         float* curvatures, float* frames, float* cov, void* ws, size_t ws_bytes, void* stream);
 int32_t mr_symmetric_eig3_host(const float* cov, int64_t M, float* eigenvalues, float* eigenvectors);
 
+/* Radius neighbourhoods (PyTorch3D ball_query), any K >= 1. For query i < L1 = lengths1[n] of p1 (N,P1,3), with
+ * r2 = radius * radius rounded once to float32 and d(i, j) the float32 squared distance of the calls above: walk
+ * j = 0 .. lengths2[n] - 1 in index order; every j with d(i, j) < r2 (strict; a nan distance never hits) takes the
+ * next free slot until K are full. dists (N,P1,K) float32 holds the hits' d and idx (N,P1,K) int32 their j: the first
+ * K in index order, neither the nearest K nor sorted by distance. Free slots and rows i >= L1 are 0 / -1. radius 0
+ * hits nothing; a negative or non-finite radius is MR_EINVAL.
+ * One launch whose workgroups each own a tile of queries and stream their cloud's targets through LDS; a hit is
+ * stored straight to its slot, a wave stops scanning a chunk once all its queries are full and a workgroup stops once
+ * all its waves are. Every thread pads its own free slots: no memset, no atomics; bitwise reproducible. Only when
+ * N * query tiles < 256 and P2 > 2048 is the target range cut into <= 16 splits (chosen from the shapes alone) and
+ * walked by two launches, a counting pass into the workspace (4 splits bytes per query) and a writing pass that
+ * starts every split at the sum of the earlier splits' counts; the result does not depend on the splits.
+ * mr_ball_query_geometry (host only) returns what the launch would use: queries per workgroup, splits, and the
+ * targets staged in LDS at a time (each pointer may be NULL).
+ *
+ * mr_ball_query_backward: mr_knn_points_backward at norm 2 and any K >= 1 (the same kernels): grad_p1[n,i] =
+ * sum_k 2 g (p1[n,i] - p2[n,idx]), grad_p2 its negative summed per target in 64-bit fixed point. Slots with idx < 0
+ * add nothing and their g is not read. Three launches and no memset: the fixed-point rows are cleared by a kernel, so
+ * a captured HIP graph can be replayed any number of times. All arguments are checked before any GPU call. */
+int32_t mr_ball_query_geometry(int64_t N, int64_t P1, int64_t P2, int32_t K, int32_t* queries_per_group,
+                               int32_t* splits, int32_t* lds_chunk);
+size_t mr_ball_query_workspace(int64_t N, int64_t P1, int64_t P2, int32_t K);
+int32_t mr_ball_query(const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2, const int64_t* lengths1,
+                      const int64_t* lengths2, float radius, int32_t K, float* dists, int32_t* idx, void* ws,
+                      size_t ws_bytes, void* stream);
+size_t mr_ball_query_backward_workspace(int64_t N, int64_t P1, int64_t P2, int32_t K);
+int32_t mr_ball_query_backward(const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2,
+                               const int64_t* lengths1, const int64_t* lengths2, int32_t K, const int32_t* idx,
+                               const float* grad_dists, float* grad_p1, float* grad_p2, void* ws, size_t ws_bytes,
+                               void* stream);
+
 /* Per-kernel timing with HIP events recorded on each launch's stream (bench.py).
  * enable=1 clears and starts collection; mr_timing_read synchronizes on the
  * recorded events and returns, per kernel id, launches and summed ms. */

@@ -1,8 +1,8 @@
 // mi355r — What the point-cloud translation units (mr_points.hip, mr_knn.hip, mr_normals.hip, mr_fps.hip,
-// mr_pointmesh.hip) share: the
+// mr_pointmesh.hip, mr_ballquery.hip) share: the
 // size limits and their host check, the clamped cloud length, the float32 distance with its fixed operation order, the
 // packed (distance, index) key, the fixed-point rows of a scatter's targets, and the brute-force nearest-point scan
-// (query load, target staging, compare loop) that k_nn, k_icp_nn, k_posed_nn, k_knn and k_frames are built from.
+// (query load, target staging, compare loop) that k_nn, k_icp_nn, k_posed_nn, k_knn, k_frames and k_ball are built from.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -16,6 +16,7 @@
 //   k_knn_bwd     one thread per query: grad_p1 = sum_k 2 g (p1 - p2[idx]) (norm 1: g sign(.)) with a plain store, and
 //                 the same addends into the targets' rows with 64-bit fixed-point integer atomics (mr_common.h);
 //   k_knn_bwd_p2  grad_p2 = -(row). Slots with idx < 0 contribute nothing and their g is not read.
+//   k_zero_words  clears the fixed-point rows for mr_ball_query_backward, which runs the two kernels above at any K.
 // The geometry (knn_geom), the split constants and knn_insert are mr_knn.h's, shared with mr_normals.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -165,6 +166,11 @@ __global__ void __launch_bounds__(MRK_TBLOCK) k_knn_bwd_p2(const u64* __restrict
   if (i < n) grad_p2[i] = 0.0f - fix_read(fix, rem, i);  // +0 for a target nothing reached
 }
 
+__global__ void __launch_bounds__(MRK_TBLOCK) k_zero_words(u64* __restrict__ p, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * MRK_TBLOCK + threadIdx.x;
+  if (i < n) p[i] = 0ull;
+}
+
 int check_knn(const char* who, const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2, int32_t norm,
               int32_t K) {
   if (int rc = check_sizes(who, N, P1, P2)) return rc;
@@ -267,6 +273,38 @@ int32_t mr_knn_points_backward(const float* p1, const float* p2, int64_t N, int6
   const int k = K;
   if (int rc = launch(KID_NONE, "k_knn_bwd", norm == 2 ? k_knn_bwd<2> : k_knn_bwd<1>, grid, MRK_TBLOCK, 0, st, p1, p2, P1, P2,
                       lengths1, lengths2, k, idx, grad_dists, grad_p1, w.fix, w.rem))
+    return rc;
+  return launch(KID_NONE, "k_knn_bwd_p2", k_knn_bwd_p2, (unsigned)ceil_div(3 * N * P2, MRK_TBLOCK), MRK_TBLOCK, 0, st,
+                (const u64*)w.fix, (const float*)w.rem, 3 * N * P2, grad_p2);
+}
+
+// The gradient of mr_ball_query's dists (mr_ballquery.hip): the squared-distance kernels above, at any K >= 1. The
+// fixed-point rows are cleared by k_zero_words, not by a memset: in a captured graph of forward + backward the memset
+// node cleared them on the first replay only (tests/test_gpu_ball_query.py replays twice with changed inputs).
+size_t mr_ball_query_backward_workspace(int64_t N, int64_t P1, int64_t P2, int32_t K) {
+  if (!sizes_ok(N, P1, P2) || K < 1) return 0;
+  return carve_fix(nullptr, 3 * N * P2).bytes;
+}
+
+int32_t mr_ball_query_backward(const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2,
+                               const int64_t* lengths1, const int64_t* lengths2, int32_t K, const int32_t* idx,
+                               const float* grad_dists, float* grad_p1, float* grad_p2, void* ws, size_t ws_bytes,
+                               void* stream) {
+  if (int rc = check_sizes("ball query backward", N, P1, P2)) return rc;
+  if (K < 1) return set_err(MR_EINVAL, "ball query backward: K must be >= 1");
+  if (!p1 || !p2 || !idx || !grad_dists || !grad_p1 || !grad_p2 || !ws)
+    return set_err(MR_EINVAL, "ball query backward: NULL pointer");
+  const FixWS w = carve_fix(ws, 3 * N * P2);
+  if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "ball query backward workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  const int64_t words = (int64_t)(w.bytes / sizeof(u64));  // the carve ends on a multiple of 256 B
+  if (int rc = launch(KID_NONE, "k_zero_words", k_zero_words, (unsigned)ceil_div(words, MRK_TBLOCK), MRK_TBLOCK, 0, st,
+                      (u64*)ws, words))
+    return rc;
+  const dim3 grid((unsigned)ceil_div(P1, MRK_TBLOCK), (unsigned)N);
+  const int k = K;
+  if (int rc = launch(KID_NONE, "k_knn_bwd", k_knn_bwd<2>, grid, MRK_TBLOCK, 0, st, p1, p2, P1, P2, lengths1, lengths2,
+                      k, idx, grad_dists, grad_p1, w.fix, w.rem))
     return rc;
   return launch(KID_NONE, "k_knn_bwd_p2", k_knn_bwd_p2, (unsigned)ceil_div(3 * N * P2, MRK_TBLOCK), MRK_TBLOCK, 0, st,
                 (const u64*)w.fix, (const float*)w.rem, 3 * N * P2, grad_p2);

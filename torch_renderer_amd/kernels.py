@@ -389,6 +389,78 @@ class KnnPoints(torch.autograd.Function):
         return g1.to(dt1), g2.to(dt2), None, None, None, None
 
 
+# --------------------------------------------------------------------------- radius neighbourhoods (csrc/mr_ballquery.hip)
+def _ball_args(K, radius):
+    K, radius = int(K), float(radius)
+    if K < 1:
+        raise ValueError("K must be >= 1")
+    if not (0.0 <= radius < float("inf")):
+        raise ValueError("ball_query: radius must be finite and >= 0")
+    return K, radius
+
+
+def ball_query_geometry(N, P1, P2, K):
+    """(queries_per_group, splits, lds_chunk) of the launches mr_ball_query makes for these shapes (host only)."""
+    out = [ctypes.c_int32() for _ in range(3)]
+    check(_lib.load().mr_ball_query_geometry(int(N), int(P1), int(P2), int(K), *(ctypes.byref(o) for o in out)))
+    return tuple(o.value for o in out)
+
+
+def _ball_forward(p1f, p2f, l1, l2, N, P1, P2, K, radius):
+    L = _lib.load()
+    dev = p1f.device
+    dists = torch.empty((N, P1, K), device=dev)
+    idx = torch.empty((N, P1, K), dtype=torch.int32, device=dev)
+    wsb = _ws_size(L.mr_ball_query_workspace, N, P1, P2, K)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    check(L.mr_ball_query(ptr(p1f), ptr(p2f), N, P1, P2, ptr(l1), ptr(l2), radius, K, ptr(dists), ptr(idx), ptr(ws),
+                          wsb, _lib.stream_handle(dev)))
+    return dists, idx
+
+
+def ball_query(p1, p2, lengths1=None, lengths2=None, K=500, radius=0.2):
+    """(dists (N,P1,K) float32, idx (N,P1,K) int32): for every point of p1 (N,P1,3) the first K points of
+    p2[n, :lengths2[n]], in index order, whose float32 squared distance (nearest_points') is < float32(radius)^2;
+    dists holds those distances, unsorted. Free slots and rows past lengths1[n] are 0 / -1. Any K >= 1. No autograd;
+    one launch, or a counting and a writing pass when the shapes alone cannot fill the chip (mr_ball_query)."""
+    K, radius = _ball_args(K, radius)
+    p1f, p2f, l1, l2, N, P1, P2 = _cloud_args(p1, p2, lengths1, lengths2, 2)
+    return _ball_forward(p1f, p2f, l1, l2, N, P1, P2, K, radius)
+
+
+class BallQuery(torch.autograd.Function):
+    """ball_query with the gradient of ``dists`` w.r.t. p1 and p2 (``idx`` is not differentiable): three launches
+    backward and no memset, the many-to-one p2 side summed in fixed point (mr_ball_query_backward)."""
+
+    @staticmethod
+    def forward(ctx, p1, p2, lengths1, lengths2, K, radius):
+        K, radius = _ball_args(K, radius)
+        p1f, p2f, l1, l2, N, P1, P2 = _cloud_args(p1, p2, lengths1, lengths2, 2)
+        dists, idx = _ball_forward(p1f, p2f, l1, l2, N, P1, P2, K, radius)
+        ctx.mark_non_differentiable(idx)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(p1f, p2f, idx, l1, l2)
+        ctx.args = (K, p1.dtype, p2.dtype)
+        return dists, idx
+
+    @staticmethod
+    def backward(ctx, g, _g_idx):
+        if g is None:
+            return (None,) * 6
+        p1f, p2f, idx, l1, l2 = ctx.saved_tensors
+        K, dt1, dt2 = ctx.args
+        g = g.detach().float().contiguous()
+        _require_cuda(g)
+        L = _lib.load()
+        N, P1, P2 = p1f.shape[0], p1f.shape[1], p2f.shape[1]
+        g1, g2 = torch.empty_like(p1f), torch.empty_like(p2f)
+        wsb = _ws_size(L.mr_ball_query_backward_workspace, N, P1, P2, K)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=p1f.device)
+        check(L.mr_ball_query_backward(ptr(p1f), ptr(p2f), N, P1, P2, ptr(l1), ptr(l2), K, ptr(idx), ptr(g), ptr(g1),
+                                       ptr(g2), ptr(ws), wsb, _lib.stream_handle(p1f.device)))
+        return g1.to(dt1), g2.to(dt2), None, None, None, None
+
+
 # --------------------------------------------------------------------------- farthest points (csrc/mr_fps.hip)
 def farthest_geometry(N, P, Kmax):
     """(threads, points_per_thread, streamed) of the launch mr_farthest_points makes for these shapes (host only):

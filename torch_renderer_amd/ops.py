@@ -13,6 +13,9 @@ k_icp_* kernels of csrc/mr_points.hip). Neither is differentiable.
 
 ``knn_points`` (K <= 32 nearest neighbours, csrc/mr_knn.hip; ``dists`` is differentiable) and ``knn_gather``.
 
+``ball_query`` (the first K neighbours inside a radius, any K, csrc/mr_ballquery.hip; ``dists`` is differentiable) and
+``masked_gather``.
+
 ``sample_farthest_points`` (csrc/mr_fps.hip): one workgroup per cloud runs all K rounds on the device; the selected
 points are differentiable w.r.t. the input points.
 
@@ -254,6 +257,52 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, norm: int = 2, K: int = 1, 
     dists = dists.to(p1.dtype)
     idx = idx.clamp(min=0).long()
     return _KNN(dists=dists, idx=idx, knn=knn_gather(p2, idx, lengths2) if return_nn else None)
+
+
+def masked_gather(points, idx):
+    """``pytorch3d.ops.utils.masked_gather``: points (N,P,U) gathered at idx (N,L,K) -> (N,L,K,U), or at idx (N,L) ->
+    (N,L,U), with zeros wherever idx < 0 (ball_query's padding). Differentiable w.r.t. points. The indices are
+    clamped before torch's gather, so a -1 never reaches it, and nothing is read back from the device."""
+    if points.dim() != 3 or idx.dim() not in (2, 3):
+        raise ValueError("masked_gather: points must be (N, P, U) and idx (N, L, K) or (N, L)")
+    if points.shape[0] != idx.shape[0]:
+        raise ValueError("points and idx must have the same batch dimension")
+    U = points.shape[2]
+    pad = idx < 0
+    safe = idx.clamp(min=0).long()
+    if idx.dim() == 2:
+        out = points.gather(1, safe[..., None].expand(-1, -1, U))
+    else:
+        out = points[:, :, None].expand(-1, -1, idx.shape[2], -1).gather(1, safe[..., None].expand(-1, -1, -1, U))
+    return out.masked_fill(pad[..., None], 0.0)
+
+
+def ball_query(p1, p2, lengths1=None, lengths2=None, K: int = 500, radius: float = 0.2, return_nn: bool = True):
+    """``pytorch3d.ops.ball_query``: for every point of p1 (N,P1,3) the first K points of p2 (N,P2,3), in index order,
+    that lie inside ``radius``, as a namedtuple (dists (N,P1,K), idx (N,P1,K) int64, knn (N,P1,K,3) or None).
+
+    For query i of cloud n, with L1 = lengths1[n] (or P1), L2 = lengths2[n] (or P2) and r2 = float32(radius)^2 rounded
+    once to float32: j = 0 .. L2 - 1 are walked in index order and every j whose float32 squared distance
+    (dx*dx + dy*dy) + dz*dz is < r2 (strict) takes the next free slot until K are full. The result is the first K in
+    index order, not the K nearest, and is not sorted by distance; dists holds the hits' squared distances. Free slots
+    and rows i >= L1 are idx = -1, dists = 0, knn = 0 (knn_points pads idx with 0 instead). radius 0 hits nothing, a
+    nan coordinate never hits; a negative or non-finite radius raises ValueError. Coordinates are read as float32;
+    dists and knn come back in p1's dtype. Any K >= 1.
+
+    dists is differentiable w.r.t. p1 and p2 (kernels.BallQuery, csrc/mr_ballquery.hip), knn through masked_gather.
+    Nothing synchronises; forward and backward capture into a HIP graph."""
+    if p1.dim() != 3 or p2.dim() != 3:
+        raise ValueError("p1 and p2 must be (N, P, D) tensors.")
+    if p1.shape[0] != p2.shape[0]:
+        raise ValueError("p1 and p2 must have the same batch dimension.")
+    if p1.shape[2] != p2.shape[2]:
+        raise ValueError("p1 and p2 must have the same point dimension.")
+    for l in (lengths1, lengths2):
+        if l is not None and tuple(l.shape) != (p1.shape[0],):
+            raise ValueError("lengths must be of shape (N,)")
+    dists, idx = kernels.BallQuery.apply(p1, p2, lengths1, lengths2, K, radius)
+    idx = idx.long()
+    return _KNN(dists=dists.to(p1.dtype), idx=idx, knn=masked_gather(p2, idx).to(p1.dtype) if return_nn else None)
 
 
 def sample_farthest_points(points, lengths=None, K=50, random_start_point: bool = False):
