@@ -505,6 +505,38 @@ int32_t mr_icp_iterate(const float* x, const float* y, int64_t N, int64_t P1, in
                        int32_t iterations, float* rts, float* history, float* rmse, int32_t* status, void* ws,
                        size_t ws_bytes, void* stream);
 int32_t mr_icp_transform(const float* x, int64_t N, int64_t P, const float* rts, float* out, void* stream);
+
+/* Point-to-plane ICP: a second estimator on the loop of mr_icp_iterate, rigid (s stays what mr_icp_init set).
+ * mr_icp_init and mr_icp_transform are used as they are, with a workspace of mr_icp_plane_workspace bytes (it begins
+ * with mr_icp_workspace's layout). y_normals (N,P2,3) are used as given: a zero normal contributes nothing, a
+ * normal's sign does not matter. max_dist2 is the float32 square of the maximum correspondence distance, or +inf.
+ * Per cloud, with L1, L2 its lengths and (R, T, s) = rts, every iteration:
+ *  1. p_i = s (x_i R) + T in float32 (the transform code above), i < L1; j(i) the nearest target j < L2 by the float32
+ *     squared distance (dx*dx + dy*dy) + dz*dz, the lowest index on ties (mr_icp_iterate's search). A pair is valid
+ *     iff that distance is <= max_dist2 (+inf: every pair); m counts the valid pairs.
+ *  2. In float64 and a fixed order: c = s (mx R) + T, mx the mean of the cloud's source points; per valid pair with
+ *     q = y_j, n = y_normals_j: r = (p - q).n, J = [(p - c) x n, n] (6); A = sum J J^T, b = sum J r.
+ *  3. xi = (w, t) solves (A + lam I) xi = -b, lam = 1e-9 trace(A) / 6, by a 6x6 Cholesky in float64; xi = 0 when
+ *     trace(A) is not > 0 (m = 0 included), a pivot is not > 0 or the solution is not finite. E = exp([w]x) by
+ *     Rodrigues in float64 (below |w| = 1e-4 the series sin(th)/th = 1 - th^2/6, (1 - cos th)/th^2 = 1/2 - th^2/24).
+ *  4. R <- R E^T, T <- (T - c) E^T + c + t (row vectors), s unchanged: formed in float64 from the float32 values and
+ *     rounded once to float32, into rts and slot status[1] of history. xi = 0 keeps rts bit for bit.
+ *  5. rmse = float32(sqrt(sum_valid ((p'_i - q_i).n_i)^2 / max(m, 1))), p' the float32 transform code with the new
+ *     rts; correspondences and validity are this iteration's.
+ *  6. rel = (previous rmse - rmse) / previous rmse in float32, 1 on the first iteration; a cloud is done when
+ *     rel <= relative_rmse_thr (a NaN does not pass) or m == 0 (it keeps its transform and reports rmse 0).
+ *     status[0] becomes 1 when every cloud is done in the same iteration. status words, idle kernels, batching of
+ *     the status reads and the independence of the results from the batch size: as mr_icp_iterate.
+ * Four launches an iteration, no (N,P1,P2) matrix, no host read. mr_icp_plane_solve_host (host only, no GPU) runs
+ * steps 3-4, the code the kernel runs, on one system: A21 the upper triangle of A row by row, b6, rts_in (13),
+ * c3 -> rts_out (13). */
+size_t mr_icp_plane_workspace(int64_t N, int64_t P1, int64_t P2);
+int32_t mr_icp_plane_iterate(const float* x, const float* y, const float* y_normals, int64_t N, int64_t P1, int64_t P2,
+                             const int64_t* x_lengths, const int64_t* y_lengths, float max_dist2,
+                             float relative_rmse_thr, int32_t max_iterations, int32_t iterations, float* rts,
+                             float* history, float* rmse, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+int32_t mr_icp_plane_solve_host(const double* A21, const double* b6, const float* rts_in, const double* c3,
+                                float* rts_out);
 size_t mr_points_alignment_workspace(int64_t N, int64_t P);
 int32_t mr_points_alignment(const float* x, const float* y, int64_t N, int64_t P, const int64_t* lengths,
                             const float* weights, int32_t flags, double eps, float* rts, void* ws, size_t ws_bytes,

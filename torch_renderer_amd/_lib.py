@@ -194,6 +194,10 @@ _SIGS = [
     ("mr_icp_iterate", _I32, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, _I32, ctypes.c_float, _I32, _I32, _VP, _VP, _VP,
                               _VP, _VP, _SZ, _VP]),
     ("mr_icp_transform", _I32, [_VP, _I64, _I64, _VP, _VP, _VP]),
+    ("mr_icp_plane_workspace", _SZ, [_I64, _I64, _I64]),
+    ("mr_icp_plane_iterate", _I32, [_VP, _VP, _VP, _I64, _I64, _I64, _VP, _VP, ctypes.c_float, ctypes.c_float, _I32,
+                                    _I32, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    ("mr_icp_plane_solve_host", _I32, [_VP, _VP, _VP, _VP, _VP]),
     ("mr_points_alignment_workspace", _SZ, [_I64, _I64]),
     ("mr_points_alignment", _I32, [_VP, _VP, _I64, _I64, _VP, _VP, _I32, ctypes.c_double, _VP, _VP, _SZ, _VP]),
     ("mr_sample_points_forward", _I32, [_VP, _I64, _VP, _I64, _VP, _VP, _I64, _VP, _VP]),

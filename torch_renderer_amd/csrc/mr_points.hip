@@ -26,7 +26,11 @@
 //                   Procrustes problem by a fixed-sweep Jacobi SVD in float64, then sums its tile of the residual
 //                   under the new transform) and k_icp_status (rmse, relative drop, the device status words every
 //                   kernel of a later iteration reads first). No float atomics, every sum in a fixed order.
-//   k_posed_*       the chamfer distance of ONE cloud pair under S poses (mr_posed_chamfer): k_posed_nn, a workgroup
+//   k_icp_plane_*   the point-to-plane estimator on the same loop (mr_icp_plane_iterate): k_icp_nn as it is, then
+//                   k_icp_plane_moments (validity, float64 sums of J J^T, J r and the pair count per tile),
+//                   k_icp_plane_solve (a damped 6x6 Cholesky step about the transformed source mean, then the new
+//                   residual) and k_icp_plane_status (the pair count as divisor).
+//   k_posed_*     the chamfer distance of ONE cloud pair under S poses (mr_posed_chamfer): k_posed_nn, a workgroup
 //                   per (pose, direction, 512 queries) that scans all targets itself, and k_posed_final (see there).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -772,9 +776,259 @@ __global__ void __launch_bounds__(MRR_BLOCK) k_icp_apply(const float* __restrict
 }
 
 // ---------------------------------------------------------------------------
+// Point-to-plane ICP (mr_icp_plane_iterate): a second estimator on the loop above. k_icp_nn is launched as it is;
+// k_icp_plane_moments sums the Gauss-Newton normal equations of the valid pairs, k_icp_plane_solve takes one damped
+// step about the transformed source mean and sums the new residual, k_icp_plane_status divides by the pair count.
+// The rule is stated in include/mi355r.h.
+// ---------------------------------------------------------------------------
+#define MRI_PMOM 28     // per-workgroup sums (double): A's upper triangle row by row (21), b (6), the pair count m
+
+struct IcpPlaneWS {
+  IcpWS icp;      // mr_icp_init's layout comes first: the init is shared
+  double* pmom;   // (N, nblk, MRI_PMOM)
+  double* cnt;    // (N) valid pairs of this iteration
+  float* prev;    // (N, MRI_RTS) the transform the iteration started from (rts is overwritten while tiles still solve)
+  size_t bytes;
+};
+IcpPlaneWS carve_icp_plane(void* base, int64_t N, int64_t P1) {
+  IcpPlaneWS w;
+  w.icp = carve_icp(base, N, P1);
+  Carver c(base, w.icp.bytes);
+  w.pmom = c.take<double>((size_t)(N * w.icp.nblk * MRI_PMOM));
+  w.cnt = c.take<double>((size_t)N);
+  w.prev = c.take<float>((size_t)(N * MRI_RTS));
+  w.bytes = c.off;
+  return w;
+}
+
+// c = s (mx R) + T in float64 from the float32 transform t and the cloud's constants (xc[1..3] = mx).
+__host__ __device__ __forceinline__ void plane_centre(const double* __restrict__ xc, const float* __restrict__ t,
+                                                      double (&c)[3]) {
+  const double s = (double)t[12];
+  for (int b = 0; b < 3; ++b)
+    c[b] = s * ((xc[1] * (double)t[b] + xc[2] * (double)t[3 + b]) + xc[3] * (double)t[6 + b]) + (double)t[9 + b];
+}
+
+// Steps 3 and 4 of the rule, in float64: xi = (w, t) solves (A + lam I) xi = -b, lam = 1e-9 trace(A) / 6, by a 6x6
+// Cholesky; E = exp([w]x) by Rodrigues (the series 1 - th^2/6, 1/2 - th^2/24 below th = 1e-4); R <- R E^T,
+// T <- (T - c) E^T + c + t, s as it is, rounded once to float32. A: the 21 entries of the upper triangle row by row.
+// trace(A) not > 0 (no pair, only zero normals, a NaN), a pivot not > 0 or a non-finite solution: xi = 0 and `out`
+// is `in`, bit for bit.
+// (Also a host function: mr_icp_plane_solve_host.)
+__host__ __device__ void plane_step(const double* __restrict__ A, const double* __restrict__ b,
+                                    const float* __restrict__ in, const double (&c)[3], float* out) {
+  double L[6][6], xi[6];
+  double tr = 0.0;
+  {
+    int e = 0;
+    for (int i = 0; i < 6; ++i)
+      for (int j = i; j < 6; ++j) {
+        L[i][j] = L[j][i] = A[e++];
+        if (i == j) tr += L[i][i];
+      }
+  }
+  bool ok = tr > 0.0;
+  if (ok) {
+    const double lam = 1e-9 * tr / 6.0;
+    for (int j = 0; j < 6 && ok; ++j) {  // the lower triangle becomes the Cholesky factor
+      double d = L[j][j] + lam;
+      for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+      ok = d > 0.0;
+      if (!ok) break;
+      d = sqrt(d);
+      L[j][j] = d;
+      for (int i = j + 1; i < 6; ++i) {
+        double v = L[i][j];
+        for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+        L[i][j] = v / d;
+      }
+    }
+  }
+  if (ok) {
+    for (int i = 0; i < 6; ++i) {  // L z = -b
+      double v = -b[i];
+      for (int k = 0; k < i; ++k) v -= L[i][k] * xi[k];
+      xi[i] = v / L[i][i];
+    }
+    for (int i = 5; i >= 0; --i) {  // L^T xi = z
+      double v = xi[i];
+      for (int k = i + 1; k < 6; ++k) v -= L[k][i] * xi[k];
+      xi[i] = v / L[i][i];
+    }
+    for (int i = 0; i < 6; ++i) ok = ok && (xi[i] - xi[i] == 0.0);  // finite
+  }
+  if (!ok) {
+    for (int k = 0; k < MRI_RTS; ++k) out[k] = in[k];
+    return;
+  }
+  const double w0 = xi[0], w1 = xi[1], w2 = xi[2];
+  const double th2 = (w0 * w0 + w1 * w1) + w2 * w2, th = sqrt(th2);
+  double ka, kb;
+  if (th < 1e-4) {
+    ka = 1.0 - th2 / 6.0;
+    kb = 0.5 - th2 / 24.0;
+  } else {
+    ka = sin(th) / th;
+    kb = (1.0 - cos(th)) / th2;
+  }
+  const double dg = 1.0 - kb * th2;
+  const double E[3][3] = {{dg + kb * w0 * w0, kb * w0 * w1 - ka * w2, kb * w0 * w2 + ka * w1},
+                          {kb * w1 * w0 + ka * w2, dg + kb * w1 * w1, kb * w1 * w2 - ka * w0},
+                          {kb * w2 * w0 - ka * w1, kb * w2 * w1 + ka * w0, dg + kb * w2 * w2}};
+  for (int a = 0; a < 3; ++a)
+    for (int k = 0; k < 3; ++k)
+      out[3 * a + k] = (float)(((double)in[3 * a] * E[k][0] + (double)in[3 * a + 1] * E[k][1]) +
+                               (double)in[3 * a + 2] * E[k][2]);
+  const double u0 = (double)in[9] - c[0], u1 = (double)in[10] - c[1], u2 = (double)in[11] - c[2];
+  for (int k = 0; k < 3; ++k) out[9 + k] = (float)((((u0 * E[k][0] + u1 * E[k][1]) + u2 * E[k][2]) + c[k]) + xi[3 + k]);
+  out[12] = in[12];
+}
+
+// grid (nblk, N), k_icp_moments' layout: a tile of source points. Decodes key -> (distance, index) and sets the key
+// back to all-ones; a pair is valid when the index is inside the target and the distance is <= max_dist2 (+inf: every
+// pair); idx gets the index, -1 for no valid pair. Per valid pair, p = sim_apply(x_i), q = y_j, n = yn_j:
+// r = (p - q).n, J = [(p - c) x n, n], and the workgroup's sums of J J^T (upper triangle), J r and 1 go to pmom.
+// Workgroup 0 of a cloud also copies the transform to prev for k_icp_plane_solve.
+__global__ void __launch_bounds__(MRR_BLOCK) k_icp_plane_moments(
+    const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ yn, int64_t P1, int64_t P2,
+    const int64_t* __restrict__ xl, const int64_t* __restrict__ yl, const double* __restrict__ xc,
+    const float* __restrict__ rts, float max_dist2, const int32_t* __restrict__ status, int max_iter,
+    u64* __restrict__ key, int32_t* __restrict__ idx, float* __restrict__ prev, double* __restrict__ pmom,
+    int64_t nblk) {
+  __shared__ double sm[4 * MRI_PMOM];
+  if (icp_idle(status, max_iter)) return;
+  const int64_t n = blockIdx.y;
+  const int64_t lx = cloud_len(xl, n, P1), lt = cloud_len(yl, n, P2);
+  const float* __restrict__ tr = rts + n * MRI_RTS;
+  if (blockIdx.x == 0 && threadIdx.x < MRI_RTS) prev[n * MRI_RTS + threadIdx.x] = tr[threadIdx.x];
+  double c[3];
+  plane_centre(xc + n * MRI_XC, tr, c);
+  const bool every = max_dist2 == __builtin_inff();
+  double a[MRI_PMOM];
+#pragma unroll
+  for (int k = 0; k < MRI_PMOM; ++k) a[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k < MRR_PER; ++k) {
+    const int64_t i = (int64_t)blockIdx.x * MRR_TILE + k * MRR_BLOCK + threadIdx.x;
+    if (i >= P1) continue;
+    int64_t j = -1;
+    if (i < lx) {
+      const u64 kk = key[n * P1 + i];
+      key[n * P1 + i] = ~0ull;
+      j = (int64_t)key_index(kk);
+      if (j >= lt || !(every || key_dist(kk) <= max_dist2)) j = -1;  // an empty target leaves the key untouched
+    }
+    idx[n * P1 + i] = (int32_t)j;
+    if (j < 0) continue;
+    const float* __restrict__ q = x + 3 * (n * P1 + i);
+    const float* __restrict__ t = y + 3 * (n * P2 + j);
+    const float* __restrict__ nn = yn + 3 * (n * P2 + j);
+    float p0, p1, p2;
+    sim_apply(tr, q[0], q[1], q[2], p0, p1, p2);
+    const double n0 = (double)nn[0], n1 = (double)nn[1], n2 = (double)nn[2];
+    const double d0 = (double)p0 - (double)t[0], d1 = (double)p1 - (double)t[1], d2 = (double)p2 - (double)t[2];
+    const double u0 = (double)p0 - c[0], u1 = (double)p1 - c[1], u2 = (double)p2 - c[2];
+    const double r = (d0 * n0 + d1 * n1) + d2 * n2;
+    const double J[6] = {u1 * n2 - u2 * n1, u2 * n0 - u0 * n2, u0 * n1 - u1 * n0, n0, n1, n2};
+    int e = 0;
+#pragma unroll
+    for (int v = 0; v < 6; ++v)
+#pragma unroll
+      for (int w = v; w < 6; ++w) a[e++] += J[v] * J[w];
+#pragma unroll
+    for (int v = 0; v < 6; ++v) a[21 + v] += J[v] * r;
+    a[27] += 1.0;
+  }
+  block_sums<MRR_BLOCK / 64>(a, sm);
+  if (threadIdx.x < MRI_PMOM) {
+    double v = 0.0;
+#pragma unroll
+    for (int k = 0; k < MRI_PMOM; ++k) v = threadIdx.x == k ? a[k] : v;
+    pmom[(n * nblk + blockIdx.x) * MRI_PMOM + threadIdx.x] = v;
+  }
+}
+
+// grid (nblk, N). Thread 0 of every workgroup sums its cloud's partials in order and takes the step from prev (the
+// same inputs and code: the same bits in every workgroup of the cloud); workgroup 0 stores the transform in rts and
+// in slot status[1] of the history, and the pair count in cnt. Then the workgroup's tile of the new residual
+// sum ((p' - q).n)^2 over this iteration's valid pairs, p' = sim_apply of the new transform.
+__global__ void __launch_bounds__(MRR_BLOCK) k_icp_plane_solve(
+    const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ yn, int64_t N, int64_t P1,
+    int64_t P2, const int64_t* __restrict__ xl, const double* __restrict__ xc, const double* __restrict__ pmom,
+    int64_t nblk, const int32_t* __restrict__ idx, const float* __restrict__ prev, const int32_t* __restrict__ status,
+    int max_iter, float* __restrict__ rts, float* __restrict__ hist, double* __restrict__ cnt,
+    double* __restrict__ res) {
+  __shared__ double sm[4];
+  __shared__ float tr[MRI_RTS];
+  if (icp_idle(status, max_iter)) return;
+  const int64_t n = blockIdx.y;
+  if (threadIdx.x == 0) {
+    double m[MRI_PMOM];
+    for (int k = 0; k < MRI_PMOM; ++k) m[k] = 0.0;
+    for (int64_t b = 0; b < nblk; ++b)
+      for (int k = 0; k < MRI_PMOM; ++k) m[k] += pmom[(n * nblk + b) * MRI_PMOM + k];
+    double c[3];
+    plane_centre(xc + n * MRI_XC, prev + n * MRI_RTS, c);
+    plane_step(m, m + 21, prev + n * MRI_RTS, c, tr);
+    if (blockIdx.x == 0) cnt[n] = m[27];
+  }
+  __syncthreads();
+  if (blockIdx.x == 0 && threadIdx.x < MRI_RTS) {
+    rts[n * MRI_RTS + threadIdx.x] = tr[threadIdx.x];
+    hist[((int64_t)status[1] * N + n) * MRI_RTS + threadIdx.x] = tr[threadIdx.x];
+  }
+  const int64_t lx = cloud_len(xl, n, P1);
+  double acc = 0.0;
+#pragma unroll
+  for (int k = 0; k < MRR_PER; ++k) {
+    const int64_t i = (int64_t)blockIdx.x * MRR_TILE + k * MRR_BLOCK + threadIdx.x;
+    if (i >= lx) continue;
+    const int32_t j = idx[n * P1 + i];
+    if (j < 0 || j >= P2) continue;
+    const float* __restrict__ q = x + 3 * (n * P1 + i);
+    const float* __restrict__ t = y + 3 * (n * P2 + j);
+    const float* __restrict__ nn = yn + 3 * (n * P2 + j);
+    float o0, o1, o2;
+    sim_apply(tr, q[0], q[1], q[2], o0, o1, o2);
+    const double d0 = (double)o0 - (double)t[0], d1 = (double)o1 - (double)t[1], d2 = (double)o2 - (double)t[2];
+    const double r = (d0 * (double)nn[0] + d1 * (double)nn[1]) + d2 * (double)nn[2];
+    acc += r * r;
+  }
+  acc = block_sum(acc, sm);
+  if (threadIdx.x == 0) res[n * nblk + blockIdx.x] = acc;
+}
+
+// k_icp_status with the pair count as divisor: rmse = sqrt(residual / max(m, 1)); a cloud without a valid pair
+// (rmse 0) counts as done. rmse holds the previous iteration's values on entry.
+__global__ void __launch_bounds__(MRR_BLOCK) k_icp_plane_status(const double* __restrict__ res, int64_t nblk, int64_t N,
+                                                                const double* __restrict__ cnt, float thr,
+                                                                int max_iter, float* __restrict__ rmse,
+                                                                int32_t* __restrict__ status) {
+  __shared__ double sm[4];
+  if (icp_idle(status, max_iter)) return;  // uniform
+  const int it = status[1];
+  double open = 0.0;
+  for (int64_t n = threadIdx.x; n < N; n += MRR_BLOCK) {
+    double s = 0.0;
+    for (int64_t b = 0; b < nblk; ++b) s += res[n * nblk + b];
+    const double m = cnt[n];
+    const float r = (float)sqrt(s / (m > 1.0 ? m : 1.0));
+    const float prev = rmse[n];
+    const float rel = it == 0 ? 1.0f : (prev - r) / prev;
+    if (!(rel <= thr) && m != 0.0) open += 1.0;
+    rmse[n] = r;
+  }
+  open = block_sum(open, sm);  // also orders every thread's read of status[1] before its update
+  if (threadIdx.x == 0) {
+    status[1] = it + 1;
+    if (open == 0.0) status[0] = 1;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Chamfer distance of ONE cloud pair under S rigid / similarity poses (mr_posed_chamfer): x' = s (x R) + T per pose.
 // ---------------------------------------------------------------------------
-#define MRP_MOM 13      // per-workgroup pose moments (double): sum g (3), sum x^T g (9, row = x component), sum (x R).g
+#define MRP_MOM 13     // per-workgroup pose moments (double): sum g (3), sum x^T g (9, row = x component), sum (x R).g
 
 struct PosedWS {
   double* part;   // (2, S, ntile) distance sums of a workgroup's queries
@@ -1157,6 +1411,56 @@ int32_t mr_icp_transform(const float* x, int64_t N, int64_t P, const float* rts,
   if (!rts || !out) return set_err(MR_EINVAL, "icp transform: rts / out is NULL");
   return launch(KID_NONE, "k_icp_apply", k_icp_apply, dim3((unsigned)ceil_div(P, MRR_BLOCK), (unsigned)N), MRR_BLOCK, 0,
                 (hipStream_t)stream, x, P, rts, out);
+}
+
+size_t mr_icp_plane_workspace(int64_t N, int64_t P1, int64_t P2) {
+  if (!sizes_ok(N, P1, P2)) return 0;
+  return carve_icp_plane(nullptr, N, P1).bytes;
+}
+
+int32_t mr_icp_plane_iterate(const float* x, const float* y, const float* y_normals, int64_t N, int64_t P1, int64_t P2,
+                             const int64_t* x_lengths, const int64_t* y_lengths, float max_dist2,
+                             float relative_rmse_thr, int32_t max_iterations, int32_t iterations, float* rts,
+                             float* history, float* rmse, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = check_icp("icp plane", x, N, P1, P2)) return rc;
+  if (!(max_dist2 > 0.0f)) return set_err(MR_EINVAL, "icp plane: max_dist2 must be > 0 (+inf: no limit)");
+  if (max_iterations < 1 || iterations < 0 || (int64_t)max_iterations * N > (1ll << 40) / MRI_RTS)
+    return set_err(MR_EINVAL,
+                   "icp plane: max_iterations must be >= 1 (and the history addressable), iterations >= 0");
+  if (!y || !y_normals || !rts || !history || !rmse || !status || !ws)
+    return set_err(MR_EINVAL, "icp plane: NULL pointer");
+  const IcpPlaneWS w = carve_icp_plane(ws, N, P1);
+  if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "icp plane workspace too small");
+  const NNGeom g = nn_geom(N, P1, P2, MRI_WANT_GROUPS);
+  if (g.groups[0] > 0x7fffffffll) return set_err(MR_EUNSUPPORTED, "icp plane: P1 * P2 is too large for one launch");
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 gn((unsigned)g.groups[0], (unsigned)N), gt((unsigned)w.icp.nblk, (unsigned)N);
+  for (int it = 0; it < iterations; ++it) {
+    if (int rc = launch(KID_NONE, "k_icp_nn", k_icp_nn, gn, MRN_BLOCK, 0, st, x, y, g, x_lengths, y_lengths, (const float*)rts,
+                        (const int32_t*)status, max_iterations, w.icp.key))
+      return rc;
+    if (int rc = launch(KID_NONE, "k_icp_plane_moments", k_icp_plane_moments, gt, MRR_BLOCK, 0, st, x, y, y_normals, P1, P2,
+                        x_lengths, y_lengths, (const double*)w.icp.xc, (const float*)rts, max_dist2,
+                        (const int32_t*)status, max_iterations, w.icp.key, w.icp.idx, w.prev, w.pmom, w.icp.nblk))
+      return rc;
+    if (int rc = launch(KID_NONE, "k_icp_plane_solve", k_icp_plane_solve, gt, MRR_BLOCK, 0, st, x, y, y_normals, N, P1, P2,
+                        x_lengths, (const double*)w.icp.xc, (const double*)w.pmom, w.icp.nblk,
+                        (const int32_t*)w.icp.idx, (const float*)w.prev, (const int32_t*)status, max_iterations, rts,
+                        history, w.cnt, w.icp.res))
+      return rc;
+    if (int rc = launch(KID_NONE, "k_icp_plane_status", k_icp_plane_status, 1, MRR_BLOCK, 0, st, (const double*)w.icp.res,
+                        w.icp.nblk, N, (const double*)w.cnt, relative_rmse_thr, max_iterations, rmse, status))
+      return rc;
+  }
+  return MR_OK;
+}
+
+int32_t mr_icp_plane_solve_host(const double* A21, const double* b6, const float* rts_in, const double* c3,
+                                float* rts_out) {
+  if (!A21 || !b6 || !rts_in || !c3 || !rts_out) return set_err(MR_EINVAL, "icp plane solve: NULL pointer");
+  const double c[3] = {c3[0], c3[1], c3[2]};
+  plane_step(A21, b6, rts_in, c, rts_out);
+  return MR_OK;
 }
 
 size_t mr_points_alignment_workspace(int64_t N, int64_t P) {

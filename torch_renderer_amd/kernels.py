@@ -944,13 +944,10 @@ def similarity_transform(x, rts):
     return out
 
 
-def icp(x, y, x_lengths=None, y_lengths=None, init=None, max_iterations=100, relative_rmse_thr=1e-6, flags=0,
-        status_batch=None):
-    """The ICP loop on the device (mr_icp_*): (converged, iterations run, rmse (N) or None, Xt (N,P1,3), rts (N,13),
-    history (iterations,N,13)). ``init`` = (R (N,3,3), T (N,3), s (N)) or None. The host enqueues ``status_batch``
-    iterations at a time (default ICP_STATUS_BATCH) and reads two status words between the batches; the results do
-    not depend on that size."""
-    xf, yf, xl, yl, N, P1, P2 = _cloud_args(x, y, x_lengths, y_lengths, 2)
+def _icp_loop(xf, xl, N, P1, P2, init, max_iterations, status_batch, workspace_query, iterate):
+    """What icp and icp_plane share: mr_icp_init on a workspace of ``workspace_query`` bytes, then
+    ``iterate(k, rts, hist, rmse, status, ws, wsb, st)`` (the estimator's entry point for k more iterations) in batches
+    of ``status_batch`` with one read of the two device status words after each, then mr_icp_transform."""
     L = _lib.load()
     dev = xf.device
     st = _lib.stream_handle(dev)
@@ -961,7 +958,7 @@ def icp(x, y, x_lengths=None, y_lengths=None, init=None, max_iterations=100, rel
     max_iterations = int(max_iterations)
     rts = torch.empty((N, 13), device=dev)
     status = torch.empty(2, dtype=torch.int32, device=dev)
-    wsb = _ws_size(L.mr_icp_workspace, N, P1, P2)
+    wsb = _ws_size(workspace_query, N, P1, P2)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
     check(L.mr_icp_init(ptr(xf), N, P1, P2, ptr(xl), ptr(R0), ptr(T0), ptr(s0), ptr(rts), ptr(status), ptr(ws), wsb, st))
     done, iters, rmse = 0, 0, None
@@ -972,13 +969,51 @@ def icp(x, y, x_lengths=None, y_lengths=None, init=None, max_iterations=100, rel
         left = max_iterations
         while left > 0 and not done:
             k = min(batch, left)
-            check(L.mr_icp_iterate(ptr(xf), ptr(yf), N, P1, P2, ptr(xl), ptr(yl), int(flags), float(relative_rmse_thr),
-                                   max_iterations, k, ptr(rts), ptr(hist), ptr(rmse), ptr(status), ptr(ws), wsb, st))
+            check(iterate(k, ptr(rts), ptr(hist), ptr(rmse), ptr(status), ptr(ws), wsb, st))
             left -= k
             done, iters = status.tolist()  # the one synchronisation of a batch
     xt = torch.empty_like(xf)
     check(L.mr_icp_transform(ptr(xf), N, P1, ptr(rts), ptr(xt), st))
     return bool(done), iters, rmse, xt, rts, hist[:iters]
+
+
+def icp(x, y, x_lengths=None, y_lengths=None, init=None, max_iterations=100, relative_rmse_thr=1e-6, flags=0,
+        status_batch=None):
+    """The ICP loop on the device (mr_icp_*): (converged, iterations run, rmse (N) or None, Xt (N,P1,3), rts (N,13),
+    history (iterations,N,13)). ``init`` = (R (N,3,3), T (N,3), s (N)) or None. The host enqueues ``status_batch``
+    iterations at a time (default ICP_STATUS_BATCH) and reads two status words between the batches; the results do
+    not depend on that size."""
+    xf, yf, xl, yl, N, P1, P2 = _cloud_args(x, y, x_lengths, y_lengths, 2)
+    L = _lib.load()
+
+    def iterate(k, *state):
+        return L.mr_icp_iterate(ptr(xf), ptr(yf), N, P1, P2, ptr(xl), ptr(yl), int(flags), float(relative_rmse_thr),
+                                int(max_iterations), k, *state)
+
+    return _icp_loop(xf, xl, N, P1, P2, init, max_iterations, status_batch, L.mr_icp_workspace, iterate)
+
+
+def icp_plane(x, y, y_normals, x_lengths=None, y_lengths=None, init=None, max_iterations=100, relative_rmse_thr=1e-6,
+              max_correspondence_distance=None, status_batch=None):
+    """The point-to-plane ICP loop on the device (mr_icp_plane_iterate, whose rule include/mi355r.h states), shaped
+    like ``icp``: (converged, iterations run, rmse (N) or None, Xt (N,P1,3), rts (N,13), history (iterations,N,13)).
+    ``y_normals`` (N,P2,3) are read as float32 and used as given; ``max_correspondence_distance`` d (None: no limit)
+    reaches the kernels as float32(d) * float32(d) rounded once to float32. The scale of ``init`` stays fixed. The
+    results do not depend on ``status_batch``."""
+    xf, yf, xl, yl, N, P1, P2 = _cloud_args(x, y, x_lengths, y_lengths, 2)
+    if tuple(y_normals.shape) != tuple(yf.shape):
+        raise ValueError("y_normals must have y's padded shape (N, P2, 3)")
+    _require_cuda(y_normals)
+    nf = y_normals.detach().float().contiguous()
+    r2 = float("inf") if max_correspondence_distance is None else \
+        float(np.float32(max_correspondence_distance) * np.float32(max_correspondence_distance))
+    L = _lib.load()
+
+    def iterate(k, *state):
+        return L.mr_icp_plane_iterate(ptr(xf), ptr(yf), ptr(nf), N, P1, P2, ptr(xl), ptr(yl), r2,
+                                      float(relative_rmse_thr), int(max_iterations), k, *state)
+
+    return _icp_loop(xf, xl, N, P1, P2, init, max_iterations, status_batch, L.mr_icp_plane_workspace, iterate)
 
 
 def _mesh_args(verts, faces):

@@ -11,6 +11,10 @@ pytorch3d_icp_evaluation.py) take (N, P, 3) tensors or ``Pointclouds``; the ICP 
 the Procrustes solve and the convergence test run on the device (kernels.icp / kernels.points_alignment, the
 k_icp_* kernels of csrc/mr_points.hip). Neither is differentiable.
 
+``iterative_closest_point_to_plane`` is a second, rigid estimator on that loop (kernels.icp_plane, k_icp_plane_*): the
+same neighbour search, then a damped Gauss-Newton step on the point-to-plane residual against the target's normals,
+given or estimated with ``estimate_pointcloud_normals``. Not differentiable.
+
 ``knn_points`` (K <= 32 nearest neighbours, csrc/mr_knn.hip; ``dists`` is differentiable) and ``knn_gather``.
 
 ``ball_query`` (the first K neighbours inside a radius, any K, csrc/mr_ballquery.hip; ``dists`` is differentiable) and
@@ -137,6 +141,81 @@ def iterative_closest_point(X, Y, init_transform=None, max_iterations: int = 100
         (_lib.MR_ICP_ALLOW_REFLECTION if allow_reflection else 0)
     converged, iters, rmse, xt, rts, hist = kernels.icp(Xt, Yt, xl, yl, init_transform, max_iterations,
                                                         relative_rmse_thr, flags)
+    if isinstance(X, Pointclouds):
+        xt = X.update_padded(xt)
+    return ICPSolution(converged, rmse, xt, _split_rts(rts), [_split_rts(hist[i]) for i in range(iters)])
+
+
+def iterative_closest_point_to_plane(X, Y, Y_normals=None, init_transform=None, max_iterations: int = 100,
+                                     relative_rmse_thr: float = 1e-6, max_correspondence_distance=None,
+                                     neighborhood_size: int = 50):
+    """Point-to-plane ICP of X onto Y, (N,P,3) tensors or Pointclouds handled as in ``iterative_closest_point``: a
+    rigid Gauss-Newton estimator on the same device-side loop (a convention of this library; upstream has none).
+    Returns ``ICPSolution(converged, rmse (N,), Xt, RTs, t_history)``; ``rmse`` is the point-to-plane rmse below.
+
+    ``Y_normals`` (N,P2,3), Y's padded shape, is read as float32 and used as given: a zero normal contributes nothing
+    and a normal's sign does not matter. ``None`` computes ``estimate_pointcloud_normals(Y, neighborhood_size)``,
+    whose errors propagate (every target cloud needs more than ``neighborhood_size`` points); ``neighborhood_size`` is
+    ignored otherwise. ``init_transform`` is an (R, T, s) triple whose ``s`` stays fixed. With
+    ``max_correspondence_distance`` d (None, or a finite float > 0) a pair is valid iff its float32 squared distance
+    is <= r2 = float32(d) * float32(d); without, every pair is valid.
+
+    Per cloud, with L1 and L2 its lengths and (R, T, s) float32, every iteration:
+
+    1. p_i = s (x_i R) + T in float32 for i < L1; j(i) is the nearest target j < L2 by the float32 squared distance
+       (dx*dx + dy*dy) + dz*dz, ties to the lowest index; m counts the valid pairs.
+    2. In float64 and a fixed order: c = s (mx R) + T with mx the mean of the cloud's source points; per valid pair
+       with q = y_j and n = Y_normals_j: r = (p - q).n and J = [(p - c) x n, n]; A = sum J J^T, b = sum J r.
+    3. xi = (w, t) solves (A + lam I) xi = -b, lam = 1e-9 trace(A) / 6, by a 6x6 Cholesky in float64 (xi = 0 if
+       trace(A) is 0 or m is 0); E = exp([w]x) by Rodrigues in float64.
+    4. R <- R E^T, T <- (T - c) E^T + c + t in the row-vector convention, s unchanged; formed in float64 from the
+       float32 values and rounded once to float32.
+    5. rmse = float32(sqrt(sum_valid ((p'_i - q_i).n_i)^2 / max(m, 1))), p' under the new transform, with this
+       iteration's correspondences and validity.
+    6. rel = (prev - rmse) / prev in float32, 1 on the first iteration; a cloud is done when
+       rel <= ``relative_rmse_thr`` (a NaN does not pass). A cloud with m == 0 keeps its transform, reports rmse 0
+       and counts as done. ``converged``: every cloud is done in the same iteration.
+
+    Four launches an iteration, no (N, P1, P2) matrix, the host reads two status words every few iterations
+    (kernels.icp_plane, the k_icp_plane_* kernels of csrc/mr_points.hip). Rigid only, normals as given, a brute-force
+    neighbour scan, deterministic, not differentiable."""
+    who = "iterative_closest_point_to_plane"
+    Xt, xc, xl = _clouds_and_lengths(X, who)
+    Yt, yc, yl = _clouds_and_lengths(Y, who)
+    b, dim = Xt.shape[0], Xt.shape[2]
+    if dim != Yt.shape[2] or b != Yt.shape[0]:
+        raise ValueError("Point sets X and Y have to have the same number of batches and data dimensions.")
+    if init_transform is not None:
+        try:
+            R, T, s = init_transform
+            assert tuple(R.shape) == (b, dim, dim) and tuple(T.shape) == (b, dim) and tuple(s.shape) == (b,)
+        except Exception:
+            raise ValueError("The initial transformation init_transform has to be a named tuple SimilarityTransform "
+                             "with elements (R, T, s). R are dim x dim orthonormal matrices of shape "
+                             "(minibatch, dim, dim), T is a batch of dim-dimensional translations of shape "
+                             "(minibatch, dim) and s is a batch of scalars of shape (minibatch,).") from None
+    if max_correspondence_distance is not None:
+        try:
+            d = float(max_correspondence_distance)
+        except (TypeError, ValueError):
+            d = float("nan")
+        if isinstance(max_correspondence_distance, bool) or not (0.0 < d < float("inf")):
+            raise ValueError(f"{who}: max_correspondence_distance must be None or a finite float > 0")
+        max_correspondence_distance = d
+    if dim != 3:
+        raise NotImplementedError(f"{who}: only D = 3 is built")
+    if Y_normals is not None and (not torch.is_tensor(Y_normals) or tuple(Y_normals.shape) != tuple(Yt.shape)):
+        raise ValueError(f"{who}: Y_normals must be a tensor of Y's padded shape {tuple(Yt.shape)}")
+    _refuse_grad(who, Xt, Yt, Y_normals, *(init_transform or ()))
+    if yc is not None and any(cy == 0 and cx > 0 for cx, cy in zip(xc or [Xt.shape[1]] * b, yc)):
+        raise ValueError(f"{who}: a target cloud is empty where its source is not")
+    if Y_normals is None:
+        with torch.no_grad():
+            Y_normals = estimate_pointcloud_normals(Y, neighborhood_size)
+    _require_cuda(Xt, Yt, Y_normals, *(init_transform or ()))
+    converged, iters, rmse, xt, rts, hist = kernels.icp_plane(Xt, Yt, Y_normals, xl, yl, init_transform,
+                                                              max_iterations, relative_rmse_thr,
+                                                              max_correspondence_distance)
     if isinstance(X, Pointclouds):
         xt = X.update_padded(xt)
     return ICPSolution(converged, rmse, xt, _split_rts(rts), [_split_rts(hist[i]) for i in range(iters)])
