@@ -42,7 +42,8 @@ def case(name):
 
 # the forward cases of test_gpu_knn.py::test_knn_bitwise and the K each runs at
 CASES = {"1x1": (1,), "1x3": (8,), "63x65": (1, 2, 3, 8, 16, 32), "257x1000": (5, 32), "ties": (3, 8, 12),
-         "dup": (8,), "het": (8,), "8x100x20000": (8,), "600x1x1100": (4,), "1x1000x1000": (16,)}
+         "dup": (8,), "het": (8,), "8x100x20000": (8,), "600x1x1100": (4,), "1x1000x1000": (16,),
+         "256x1x40": (2, 16, 32)}
 
 
 def sorted_dists(q, t, norm=2):

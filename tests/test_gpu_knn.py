@@ -193,3 +193,28 @@ def test_hip_graph_capture_replays_the_eager_step():
     torch.cuda.synchronize()
     for u, w in zip(eager, captured):
         assert torch.equal(u, w)
+
+
+def test_hip_graph_capture_replays_with_changed_inputs():
+    K = 8
+    g = _dev(_upstream((2, 300, K), seed=53))
+    a, b = _dev(_upstream((2, 300, 3), seed=60)), _dev(_upstream((2, 700, 3), seed=70))
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        _step(a, b, g, K)  # warm-up on the side stream: workspace sizes cached, allocator primed
+    torch.cuda.current_stream().wait_stream(s)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        captured = _step(a, b, g, K)
+    for seed in (61, 62):  # replay twice, each time with other clouds in the captured tensors
+        a.copy_(_dev(_upstream((2, 300, 3), seed=seed)))
+        b.copy_(_dev(_upstream((2, 700, 3), seed=seed + 10)))
+        graph.replay()
+        torch.cuda.synchronize()
+        got = [t.clone() for t in captured]
+        eager = _step(a, b, g, K)
+        rd, ri = KR.knn_ref(a.cpu(), b.cpu(), K=K)
+        assert torch.equal(got[1].cpu(), ri) and torch.equal(got[0].cpu().view(torch.int32), rd.view(torch.int32))
+        for u, w in zip(eager, got):
+            assert torch.equal(u, w)

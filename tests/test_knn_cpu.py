@@ -60,6 +60,10 @@ def test_named_cases_cover_the_launch_regimes(lib):
     for name, K in (("1x1", 1), ("1x3", 8), ("dup", 8)):
         qpg, splits, chunk = geom(name, K)
         assert splits == 1 and KR.case(name)[1].shape[1] <= chunk <= 1024, (name, qpg, splits, chunk)
+    # 256 clouds are never split: the buckets 2, 16 and 32 on the path where the scan writes dists / idx itself
+    for K in KR.CASES["256x1x40"]:
+        qpg, splits, chunk = geom("256x1x40", K)
+        assert splits == 1 and chunk == 40, (K, qpg, splits, chunk)
     # splits == 1, several LDS chunks and a partial last one
     qpg, splits, chunk = geom("600x1x1100", 4)
     assert splits == 1 and chunk == 1024 and 1100 % chunk != 0 and 1100 > chunk

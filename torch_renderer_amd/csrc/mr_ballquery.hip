@@ -1,11 +1,12 @@
 // mi355r — Radius neighbourhoods of point clouds (PyTorch3D ball_query): mr_ball_query / mr_ball_query_geometry of
-// include/mi355r.h. (mr_ball_query_backward launches k_knn_bwd<2> and lives beside it, in mr_knn.hip.)
+// include/mi355r.h. (mr_ball_query_backward is mr_knn.hip's neighbour_backward at norm 2.)
 //
-//   k_ball<Q, MODE>  a workgroup owns a tile of queries (Q per thread, the query load and the staging of mr_cloud.h's
-//                    scan) and walks a range of its cloud's targets in ascending LDS chunks. A query keeps ONE
-//                    register of state, the slots it has filled: a target with d < r2 is stored straight to slot
-//                    (row * K + filled) of dists / idx, so K = 500 costs a candidate nothing. There is no list, no
-//                    sort and no memset: every thread pads its own free slots with 0 / -1 when the walk is over.
+//   k_ball<Q, MODE>  a workgroup owns a tile of queries (Q per thread: mr_knn.h's scan_tile, the query load and the
+//                    staging of mr_cloud.h's scan) and walks a range of its cloud's targets in ascending LDS chunks.
+//                    A query keeps ONE register of state, the slots it has filled: a target with d < r2 is stored
+//                    straight to slot (row * K + filled) of dists / idx, so K = 500 costs a candidate nothing. There
+//                    is no list, no sort and no memset: every thread pads its own free slots with 0 / -1 when the
+//                    walk is over.
 //                    The result is the first K hits in index order, so a full query can stop: a wave tests, every
 //                    MRB_STRIDE targets, with a ballot whether a lane still has a free slot and skips the rest of the
 //                    chunk if none has (it still stages and meets every barrier), and the workgroup leaves the chunk
@@ -28,34 +29,15 @@
 
 namespace {
 
-struct BallGeom {
-  int q;           // queries per thread
-  int64_t qtiles;  // query tiles per cloud
-  int splits;
-  int64_t per;     // targets per split
-  int chunk;       // targets staged at a time
-};
-
 // Q is the largest of 4, 2, 1 that still gives every compute unit two workgroups (else 1). Below one workgroup per
-// unit, a cloud of more than two chunks is cut into splits of at least one chunk, a multiple of MRK_SPLIT_ALIGN each:
-// a shorter cloud is launch-bound either way, and the split path scans twice.
-inline BallGeom ball_geom(int64_t N, int64_t P1, int64_t P2) {
-  BallGeom g;
+// unit, mr_knn.h's split rule with two settings of its own: only a cloud of more than two chunks is cut, into splits
+// of at least one chunk. A shorter cloud is launch-bound either way, and the split path scans twice.
+inline KnnGeom ball_geom(int64_t N, int64_t P1, int64_t P2) {
+  KnnGeom g;
+  g.kb = 0;
   g.q = 4;
   while (g.q > 1 && N * ((P1 + MRN_BLOCK * g.q - 1) / (MRN_BLOCK * g.q)) < 2 * MRK_CUS) g.q /= 2;
-  g.qtiles = (P1 + MRN_BLOCK * g.q - 1) / (MRN_BLOCK * g.q);
-  g.splits = 1;
-  g.per = P2;
-  const int64_t groups = N * g.qtiles;
-  if (groups < MRK_CUS && P2 > 2 * MRN_MAXCHUNK) {
-    int64_t want = (MRK_WANT_GROUPS + groups - 1) / groups;
-    if (want > MRK_MAXSPLIT) want = MRK_MAXSPLIT;
-    int64_t per = (P2 + want - 1) / want;
-    if (per < MRN_MAXCHUNK) per = MRN_MAXCHUNK;
-    g.per = (per + MRK_SPLIT_ALIGN - 1) / MRK_SPLIT_ALIGN * MRK_SPLIT_ALIGN;
-    g.splits = (int)((P2 + g.per - 1) / g.per);
-  }
-  g.chunk = (int)(g.per < MRN_MAXCHUNK ? g.per : MRN_MAXCHUNK);
+  knn_split(g, N, P1, P2, MRN_MAXCHUNK, false);
   return g;
 }
 
@@ -74,14 +56,12 @@ __global__ void __launch_bounds__(MRN_BLOCK) k_ball(const float* __restrict__ p1
                                                     int64_t per, float* __restrict__ dists, int32_t* __restrict__ idx,
                                                     int32_t* __restrict__ cnt) {
   __shared__ float4 sm[MRN_MAXCHUNK];
-  const int64_t n = blockIdx.y;
-  const int64_t q0 = ((int64_t)blockIdx.x / splits) * (MRN_BLOCK * Q);
-  const int s = (int)((int64_t)blockIdx.x % splits);
-  const int64_t lq = cloud_len(l1, n, P1), lt = cloud_len(l2, n, P2);
+  // skip_outside is off: a tile outside its cloud starts with every c[k] = K, and `go` below ends it before a chunk
+  const ScanTile tile = scan_tile<Q>(splits, per, l1, P1, l2, P2, false);
+  const int64_t n = tile.n, q0 = tile.q0, lq = tile.lq, tb = tile.tb, te = tile.te;
+  const int s = tile.s;
   const float* __restrict__ q = p1 + 3 * n * P1;
   const float* __restrict__ t = p2 + 3 * n * P2;
-  const int64_t tb = (int64_t)s * per;
-  const int64_t te = tb + per < lt ? tb + per : lt;
 
   float qx[Q], qy[Q], qz[Q];
   int c[Q];  // slots filled so far; K for a row that takes no hits
@@ -162,16 +142,13 @@ int32_t mr_ball_query_geometry(int64_t N, int64_t P1, int64_t P2, int32_t K, int
   if (N < 1 || P1 < 1 || P2 < 1 || K < 1)
     return set_err(MR_EINVAL, "ball query geometry: N, P1, P2 and K must be >= 1");
   if (int rc = check_sizes("ball query geometry", N, P1, P2)) return rc;
-  const BallGeom g = ball_geom(N, P1, P2);
-  if (queries_per_group) *queries_per_group = MRN_BLOCK * g.q;
-  if (splits) *splits = g.splits;
-  if (lds_chunk) *lds_chunk = g.chunk;
+  geom_out(ball_geom(N, P1, P2), queries_per_group, splits, lds_chunk);
   return MR_OK;
 }
 
 size_t mr_ball_query_workspace(int64_t N, int64_t P1, int64_t P2, int32_t K) {
   if (!sizes_ok(N, P1, P2) || K < 1) return 0;
-  const BallGeom g = ball_geom(N, P1, P2);
+  const KnnGeom g = ball_geom(N, P1, P2);
   Carver c(nullptr);
   c.take<int32_t>((g.splits > 1 ? (size_t)(N * P1) * (size_t)g.splits : 0) + 1);  // never 0: 0 means out of range
   return c.off;
@@ -183,7 +160,7 @@ int32_t mr_ball_query(const float* p1, const float* p2, int64_t N, int64_t P1, i
   if (int rc = check_ball("ball query", p1, p2, N, P1, P2, radius, K)) return rc;
   if (!dists || !idx || !ws) return set_err(MR_EINVAL, "ball query: dists / idx / workspace is NULL");
   if (ws_bytes < mr_ball_query_workspace(N, P1, P2, K)) return set_err(MR_EWORKSPACE, "ball query workspace too small");
-  const BallGeom g = ball_geom(N, P1, P2);
+  const KnnGeom g = ball_geom(N, P1, P2);
   const hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)(g.qtiles * g.splits), (unsigned)N);
   const float r2 = radius * radius;

@@ -1,8 +1,8 @@
-// mi355r — What the K-deep neighbour scans (mr_knn.hip's k_knn / k_knn_merge, mr_normals.hip's k_frames /
-// k_frames_merge) share: the launch geometry with its split rule, the insertion into the register-resident ascending
-// key list, and, as functions, the scan of a target range into the lists and the merge of a query's partial lists.
-// k_knn and k_knn_merge keep these two loops written out: called as functions they compile to other code objects
-// (profiles/normals_codeobj.txt), and their instantiations are measured as they are.
+// mi355r — What the neighbour scans (mr_knn.hip's k_knn / k_knn_merge, mr_normals.hip's k_frames / k_frames_merge,
+// mr_ballquery.hip's k_ball) share, one copy of each. Host: the launch geometry (KnnGeom) with its split rule. Device:
+// the workgroup's tile of queries and range of targets (scan_tile); for the K-deep lists, the insertion into the
+// register-resident ascending key list, the scan of a target range into the lists, the store of a partial list and
+// the merge of a query's partial lists. (k_frames keeps its own tile prologue and key store: mr_normals.hip says why.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,12 +18,31 @@
 namespace {
 
 struct KnnGeom {
-  int kb, q;        // the bucket of K; queries per thread
+  int kb, q;        // the bucket of K (0: no list is kept); queries per thread
   int64_t qtiles;   // query tiles per cloud
   int splits;
   int64_t per;      // targets per split
   int chunk;        // targets staged at a time
 };
+
+// The split rule, from g.q and the shapes alone: fewer (cloud, query tile) pairs than compute units cut the target
+// range into <= MRK_MAXSPLIT splits of at least min_per targets, a multiple of MRK_SPLIT_ALIGN each. split_short:
+// whether a cloud of at most two chunks is split at all.
+inline void knn_split(KnnGeom& g, int64_t N, int64_t P1, int64_t P2, int64_t min_per, bool split_short) {
+  g.qtiles = (P1 + MRN_BLOCK * g.q - 1) / (MRN_BLOCK * g.q);
+  g.splits = 1;
+  g.per = P2;
+  const int64_t groups = N * g.qtiles;
+  if (groups < MRK_CUS && (split_short || P2 > 2 * MRN_MAXCHUNK)) {
+    int64_t want = (MRK_WANT_GROUPS + groups - 1) / groups;
+    if (want > MRK_MAXSPLIT) want = MRK_MAXSPLIT;
+    int64_t per = (P2 + want - 1) / want;
+    if (per < min_per) per = min_per;
+    g.per = (per + MRK_SPLIT_ALIGN - 1) / MRK_SPLIT_ALIGN * MRK_SPLIT_ALIGN;
+    g.splits = (int)((P2 + g.per - 1) / g.per);
+  }
+  g.chunk = (int)(g.per < MRN_MAXCHUNK ? g.per : MRN_MAXCHUNK);
+}
 
 // The bucket is the power of two K rounds up to, at least min_kb.
 inline KnnGeom knn_geom(int64_t N, int64_t P1, int64_t P2, int K, int min_kb = 1) {
@@ -31,23 +50,44 @@ inline KnnGeom knn_geom(int64_t N, int64_t P1, int64_t P2, int K, int min_kb = 1
   g.kb = min_kb;
   while (g.kb < K) g.kb *= 2;
   g.q = g.kb <= 8 ? 4 : (g.kb == 16 ? 2 : 1);
-  g.qtiles = (P1 + MRN_BLOCK * g.q - 1) / (MRN_BLOCK * g.q);
-  g.splits = 1;
-  g.per = P2;
-  const int64_t groups = N * g.qtiles;
-  if (groups < MRK_CUS) {
-    int64_t want = (MRK_WANT_GROUPS + groups - 1) / groups;
-    if (want > MRK_MAXSPLIT) want = MRK_MAXSPLIT;
-    g.per = ((P2 + want - 1) / want + MRK_SPLIT_ALIGN - 1) / MRK_SPLIT_ALIGN * MRK_SPLIT_ALIGN;
-    g.splits = (int)((P2 + g.per - 1) / g.per);
-  }
-  g.chunk = (int)(g.per < MRN_MAXCHUNK ? g.per : MRN_MAXCHUNK);
+  knn_split(g, N, P1, P2, 1, true);
   return g;
 }
 
-// The split launch's partial lists: (N, P1, splits, K) keys.
-inline size_t knn_part_bytes(int64_t N, int64_t P1, int K, const KnnGeom& g) {
-  return g.splits > 1 ? sizeof(u64) * (size_t)(N * P1) * (size_t)K * (size_t)g.splits : 0;
+// What the three *_geometry entry points report of a launch.
+inline void geom_out(const KnnGeom& g, int32_t* queries_per_group, int32_t* splits, int32_t* lds_chunk) {
+  if (queries_per_group) *queries_per_group = MRN_BLOCK * g.q;
+  if (splits) *splits = g.splits;
+  if (lds_chunk) *lds_chunk = g.chunk;
+}
+
+// The workspace of a K-deep scan: the split launch's partial lists, (N, P1, splits, K) keys. Never 0, which means
+// "out of range" to the callers of the *_workspace entry points.
+inline size_t knn_ws_bytes(int64_t N, int64_t P1, int K, const KnnGeom& g) {
+  Carver c(nullptr);
+  c.take<u64>((g.splits > 1 ? (size_t)(N * P1) * (size_t)K * (size_t)g.splits : 0) + 1);
+  return c.off;
+}
+
+// A scanning workgroup's share of grid (query tiles * splits, N): cloud n, queries from q0 of its lq, and targets
+// tb .. te of its lt, the split s. skip_outside: a tile with no query inside its cloud (uniform) scans nothing.
+struct ScanTile {
+  int64_t n, q0, lq, lt, tb, te;
+  int s;
+};
+template <int Q>
+__device__ __forceinline__ ScanTile scan_tile(int splits, int64_t per, const int64_t* l1, int64_t P1,
+                                              const int64_t* l2, int64_t P2, bool skip_outside) {
+  ScanTile c;
+  c.n = blockIdx.y;
+  c.q0 = ((int64_t)blockIdx.x / splits) * (MRN_BLOCK * Q);
+  c.s = (int)((int64_t)blockIdx.x % splits);
+  c.lq = cloud_len(l1, c.n, P1);
+  c.lt = cloud_len(l2, c.n, P2);
+  c.tb = (int64_t)c.s * per;
+  c.te = c.tb + per < c.lt ? c.tb + per : c.lt;
+  if (skip_outside && c.q0 >= c.lq) c.te = c.tb;
+  return c;
 }
 
 // c < L[KB - 1] is known: c takes its place in the ascending list and the worst key leaves. Compile-time indices only.
@@ -82,6 +122,15 @@ __device__ __forceinline__ void knn_scan(float4* __restrict__ sm, const float* _
         if (__float_as_uint(dd) < key_bits(L[k][KB - 1])) knn_insert<KB>(L[k], nn_key(dd, base + (uint32_t)j));
       }
     }
+  }
+}
+
+// The first K keys of a list into its place o of the partial lists; all-ones for a row past its length.
+template <int KB>
+__device__ __forceinline__ void knn_store_keys(const u64 (&L)[KB], bool row_ok, int K, u64* o) {
+#pragma unroll
+  for (int j = 0; j < KB; ++j) {
+    if (j < K) o[j] = row_ok ? L[j] : ~0ull;
   }
 }
 

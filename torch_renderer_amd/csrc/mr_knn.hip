@@ -1,23 +1,28 @@
 // mi355r — K nearest neighbours of point clouds (PyTorch3D knn_points, 1 <= K <= 32) and the gradient of their
 // distances: mr_knn_points / mr_knn_points_backward / mr_knn_geometry of include/mi355r.h.
 //
-//   k_knn         a workgroup owns a tile of queries (Q per thread) and scans a range of its cloud's targets itself, in
-//                 ascending LDS chunks (the query load and the staging of mr_cloud.h's scan, k_posed_nn's shape). Every
+//   k_knn         a workgroup owns a tile of queries (Q per thread) and scans a range of its cloud's targets itself
+//                 (mr_knn.h's scan_tile and knn_scan over the query load and the staging of mr_cloud.h's scan). Every
 //                 query keeps its KB smallest keys (nn_key) ascending in registers: KB is the compile-time bucket (1, 2,
 //                 4, 8, 16, 32) the requested K rounds up to, and Q = 4, 4, 4, 4, 2, 1 keeps the lists at <= 64 VGPRs.
 //                 A candidate costs one compare, its distance bits against those of the worst kept key (targets arrive
 //                 in ascending index order, so an equal distance never displaces a kept key: ties go to the lowest
 //                 index); only a smaller one runs the unrolled insertion. With splits == 1 the range is the whole
-//                 cloud and the workgroup writes dists / idx itself: no key buffer, memset, atomic or merge. Only when N * query tiles < 256 (the CUs) is the
-//                 target range cut into <= 16 splits, from the shapes alone; a workgroup then writes its K sorted keys
-//                 per query into the workspace (8 K splits bytes per query) and
-//   k_knn_merge   (one thread per query) merges a query's partial lists by key with the same insertion and decodes.
+//                 cloud and the workgroup writes dists / idx itself (knn_store): no key buffer, memset, atomic or
+//                 merge. Only when N * query tiles < 256 (the CUs) is the target range cut into <= 16 splits, from the
+//                 shapes alone; a workgroup then writes its K sorted keys per query into the workspace (8 K splits
+//                 bytes per query) and
+//   k_knn_merge   (one thread per query) merges a query's partial lists by key (knn_merge_lists) and decodes.
 //                 The key order is total, so the K kept do not depend on the splits or the chunk size.
+// The backward, neighbour_backward, is three launches and no memset, for mr_knn_points_backward and, at any K and
+// norm 2, for mr_ball_query_backward:
+//   k_zero_words  clears the fixed-point rows;
 //   k_knn_bwd     one thread per query: grad_p1 = sum_k 2 g (p1 - p2[idx]) (norm 1: g sign(.)) with a plain store, and
 //                 the same addends into the targets' rows with 64-bit fixed-point integer atomics (mr_common.h);
 //   k_knn_bwd_p2  grad_p2 = -(row). Slots with idx < 0 contribute nothing and their g is not read.
-//   k_zero_words  clears the fixed-point rows for mr_ball_query_backward, which runs the two kernels above at any K.
-// The geometry (knn_geom), the split constants and knn_insert are mr_knn.h's, shared with mr_normals.hip.
+// The geometry (knn_geom), the split constants and the list code are mr_knn.h's, shared with mr_normals.hip and
+// mr_ballquery.hip. The two bucket ladders below stay macros of this file: mr_normals.hip's run over other buckets
+// (8 .. 64) with other arguments, and one dispatcher for both would need the kernel as a template template argument.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -53,74 +58,36 @@ __global__ void __launch_bounds__(MRN_BLOCK) k_knn(const float* __restrict__ p1,
                                                    float* __restrict__ dists, int32_t* __restrict__ idx,
                                                    u64* __restrict__ part) {
   __shared__ float4 sm[MRN_MAXCHUNK];
-  const int64_t n = blockIdx.y;
-  const int64_t q0 = ((int64_t)blockIdx.x / splits) * (MRN_BLOCK * Q);
-  const int s = (int)((int64_t)blockIdx.x % splits);
-  const int64_t lq = cloud_len(l1, n, P1), lt = cloud_len(l2, n, P2);
-  const float* __restrict__ q = p1 + 3 * n * P1;
-  const float* __restrict__ t = p2 + 3 * n * P2;
-  const int64_t tb = (int64_t)s * per;
-  int64_t te = tb + per < lt ? tb + per : lt;
-  if (q0 >= lq) te = tb;  // no query of this tile is inside its cloud (uniform): nothing to scan
-
+  const ScanTile c = scan_tile<Q>(splits, per, l1, P1, l2, P2, true);
   float qx[Q], qy[Q], qz[Q];
   u64 L[Q][KB];
-  scan_load_queries(q, q0, lq, nullptr, false, qx, qy, qz);
+  scan_load_queries(p1 + 3 * c.n * P1, c.q0, c.lq, nullptr, false, qx, qy, qz);
 #pragma unroll
   for (int k = 0; k < Q; ++k)
 #pragma unroll
     for (int j = 0; j < KB; ++j) L[k][j] = ~0ull;
-  for (int64_t t0 = tb; t0 < te; t0 += MRN_MAXCHUNK) {
-    const int cnt = (int)((te - t0 < MRN_MAXCHUNK) ? te - t0 : MRN_MAXCHUNK);
-    if (t0 != tb) __syncthreads();  // the previous chunk has been read
-    scan_stage(sm, t, t0, cnt, nullptr, false);
-    __syncthreads();
-    const uint32_t base = (uint32_t)t0;
-#pragma unroll 2
-    for (int j = 0; j < cnt; ++j) {
-      const float4 p = sm[j];
-#pragma unroll
-      for (int k = 0; k < Q; ++k) {
-        const float dd = dist3<NORM>(qx[k], qy[k], qz[k], p);
-        if (__float_as_uint(dd) < key_bits(L[k][KB - 1])) knn_insert<KB>(L[k], nn_key(dd, base + (uint32_t)j));
-      }
-    }
-  }
+  knn_scan<NORM, KB, Q>(sm, p2 + 3 * c.n * P2, c.tb, c.te, qx, qy, qz, L);
 #pragma unroll
   for (int k = 0; k < Q; ++k) {
-    const int64_t i = q0 + k * MRN_BLOCK + threadIdx.x;
+    const int64_t i = c.q0 + k * MRN_BLOCK + threadIdx.x;
     if (i >= P1) continue;
-    const int64_t row = n * P1 + i;
+    const int64_t row = c.n * P1 + i;
     if (part) {
-      u64* __restrict__ o = part + (row * splits + s) * K;
-#pragma unroll
-      for (int j = 0; j < KB; ++j) {
-        if (j < K) o[j] = i < lq ? L[k][j] : ~0ull;
-      }
+      knn_store_keys<KB>(L[k], i < c.lq, K, part + (row * splits + c.s) * K);
     } else {
-      knn_store<KB>(L[k], i < lq, K, dists + row * K, idx + row * K);
+      knn_store<KB>(L[k], i < c.lq, K, dists + row * K, idx + row * K);
     }
   }
 }
 
-// One thread per row of (N, P1): its `splits` ascending lists of K keys -> the K smallest, decoded. A list's
-// remaining keys are skipped at its first key that does not enter.
+// One thread per row of (N, P1): its `splits` ascending lists of K keys -> the K smallest, decoded.
 template <int KB>
 __global__ void __launch_bounds__(MRK_TBLOCK) k_knn_merge(const u64* __restrict__ part, int64_t rows, int K, int splits,
                                                           float* __restrict__ dists, int32_t* __restrict__ idx) {
   const int64_t row = (int64_t)blockIdx.x * MRK_TBLOCK + threadIdx.x;
   if (row >= rows) return;
   u64 L[KB];
-#pragma unroll
-  for (int j = 0; j < KB; ++j) L[j] = ~0ull;
-  for (int s = 0; s < splits; ++s) {
-    const u64* __restrict__ p = part + (row * splits + s) * K;
-    for (int j = 0; j < K; ++j) {
-      const u64 c = p[j];
-      if (!(c < L[KB - 1])) break;
-      knn_insert<KB>(L, c);
-    }
-  }
+  knn_merge_lists<KB>(part, row, K, splits, L);
   knn_store<KB>(L, true, K, dists + row * K, idx + row * K);
 }
 
@@ -181,6 +148,37 @@ int check_knn(const char* who, const float* p1, const float* p2, int64_t N, int6
   return MR_OK;
 }
 
+// The gradient of a neighbour search's dists behind mr_knn_points_backward and mr_ball_query_backward, whose own
+// checks of the sizes, K and norm have passed: k_zero_words clears the fixed-point rows, then the two kernels above.
+// A kernel clears them, not a memset: in a captured graph of forward + backward a memset node cleared them on the
+// first replay only (tests/test_gpu_knn.py and test_gpu_ball_query.py replay twice with changed inputs).
+size_t neighbour_backward_workspace(int64_t N, int64_t P1, int64_t P2, int32_t K, int32_t max_k) {
+  if (!sizes_ok(N, P1, P2) || K < 1 || K > max_k) return 0;
+  return carve_fix(nullptr, 3 * N * P2).bytes;
+}
+
+int neighbour_backward(const char* who, int32_t norm, int32_t K, const float* p1, const float* p2, int64_t N,
+                       int64_t P1, int64_t P2, const int64_t* lengths1, const int64_t* lengths2, const int32_t* idx,
+                       const float* grad_dists, float* grad_p1, float* grad_p2, void* ws, size_t ws_bytes,
+                       void* stream) {
+  if (!p1 || !p2 || !idx || !grad_dists || !grad_p1 || !grad_p2 || !ws)
+    return set_err(MR_EINVAL, "%s: NULL pointer", who);
+  const FixWS w = carve_fix(ws, 3 * N * P2);
+  if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "%s workspace too small", who);
+  const hipStream_t st = (hipStream_t)stream;
+  const int64_t words = (int64_t)(w.bytes / sizeof(u64));  // the carve ends on a multiple of 256 B
+  if (int rc = launch(KID_NONE, "k_zero_words", k_zero_words, (unsigned)ceil_div(words, MRK_TBLOCK), MRK_TBLOCK, 0, st,
+                      (u64*)ws, words))
+    return rc;
+  const dim3 grid((unsigned)ceil_div(P1, MRK_TBLOCK), (unsigned)N);
+  const int k = K;
+  if (int rc = launch(KID_NONE, "k_knn_bwd", norm == 2 ? k_knn_bwd<2> : k_knn_bwd<1>, grid, MRK_TBLOCK, 0, st, p1, p2, P1, P2,
+                      lengths1, lengths2, k, idx, grad_dists, grad_p1, w.fix, w.rem))
+    return rc;
+  return launch(KID_NONE, "k_knn_bwd_p2", k_knn_bwd_p2, (unsigned)ceil_div(3 * N * P2, MRK_TBLOCK), MRK_TBLOCK, 0, st,
+                (const u64*)w.fix, (const float*)w.rem, 3 * N * P2, grad_p2);
+}
+
 }  // namespace
 
 extern "C" {
@@ -190,18 +188,13 @@ int32_t mr_knn_geometry(int64_t N, int64_t P1, int64_t P2, int32_t K, int32_t* q
   if (N < 1 || P1 < 1 || P2 < 1 || K < 1) return set_err(MR_EINVAL, "knn geometry: N, P1, P2 and K must be >= 1");
   if (K > MRK_MAXK) return set_err(MR_EUNSUPPORTED, "knn geometry: K > %d is not built", MRK_MAXK);
   if (int rc = check_sizes("knn geometry", N, P1, P2)) return rc;
-  const KnnGeom g = knn_geom(N, P1, P2, K);
-  if (queries_per_group) *queries_per_group = MRN_BLOCK * g.q;
-  if (splits) *splits = g.splits;
-  if (lds_chunk) *lds_chunk = g.chunk;
+  geom_out(knn_geom(N, P1, P2, K), queries_per_group, splits, lds_chunk);
   return MR_OK;
 }
 
 size_t mr_knn_points_workspace(int64_t N, int64_t P1, int64_t P2, int32_t K) {
   if (!sizes_ok(N, P1, P2) || K < 1 || K > MRK_MAXK) return 0;
-  Carver c(nullptr);
-  c.take<u64>(knn_part_bytes(N, P1, K, knn_geom(N, P1, P2, K)) / sizeof(u64) + 1);  // never 0: 0 means out of range
-  return c.off;
+  return knn_ws_bytes(N, P1, K, knn_geom(N, P1, P2, K));
 }
 
 int32_t mr_knn_points(const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2, const int64_t* lengths1,
@@ -255,8 +248,7 @@ int32_t mr_knn_points(const float* p1, const float* p2, int64_t N, int64_t P1, i
 }
 
 size_t mr_knn_points_backward_workspace(int64_t N, int64_t P1, int64_t P2, int32_t K) {
-  if (!sizes_ok(N, P1, P2) || K < 1 || K > MRK_MAXK) return 0;
-  return carve_fix(nullptr, 3 * N * P2).bytes;
+  return neighbour_backward_workspace(N, P1, P2, K, MRK_MAXK);
 }
 
 int32_t mr_knn_points_backward(const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2,
@@ -264,26 +256,13 @@ int32_t mr_knn_points_backward(const float* p1, const float* p2, int64_t N, int6
                                const int32_t* idx, const float* grad_dists, float* grad_p1, float* grad_p2, void* ws,
                                size_t ws_bytes, void* stream) {
   if (int rc = check_knn("knn points backward", p1, p2, N, P1, P2, norm, K)) return rc;
-  if (!idx || !grad_dists || !grad_p1 || !grad_p2 || !ws) return set_err(MR_EINVAL, "knn points backward: NULL pointer");
-  const FixWS w = carve_fix(ws, 3 * N * P2);
-  if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "knn points backward workspace too small");
-  const hipStream_t st = (hipStream_t)stream;
-  if (int rc = memset_async(ws, 0, w.bytes, st)) return rc;
-  const dim3 grid((unsigned)ceil_div(P1, MRK_TBLOCK), (unsigned)N);
-  const int k = K;
-  if (int rc = launch(KID_NONE, "k_knn_bwd", norm == 2 ? k_knn_bwd<2> : k_knn_bwd<1>, grid, MRK_TBLOCK, 0, st, p1, p2, P1, P2,
-                      lengths1, lengths2, k, idx, grad_dists, grad_p1, w.fix, w.rem))
-    return rc;
-  return launch(KID_NONE, "k_knn_bwd_p2", k_knn_bwd_p2, (unsigned)ceil_div(3 * N * P2, MRK_TBLOCK), MRK_TBLOCK, 0, st,
-                (const u64*)w.fix, (const float*)w.rem, 3 * N * P2, grad_p2);
+  return neighbour_backward("knn points backward", norm, K, p1, p2, N, P1, P2, lengths1, lengths2, idx, grad_dists,
+                            grad_p1, grad_p2, ws, ws_bytes, stream);
 }
 
-// The gradient of mr_ball_query's dists (mr_ballquery.hip): the squared-distance kernels above, at any K >= 1. The
-// fixed-point rows are cleared by k_zero_words, not by a memset: in a captured graph of forward + backward the memset
-// node cleared them on the first replay only (tests/test_gpu_ball_query.py replays twice with changed inputs).
+// The gradient of mr_ball_query's dists (mr_ballquery.hip): squared distances, at any K >= 1.
 size_t mr_ball_query_backward_workspace(int64_t N, int64_t P1, int64_t P2, int32_t K) {
-  if (!sizes_ok(N, P1, P2) || K < 1) return 0;
-  return carve_fix(nullptr, 3 * N * P2).bytes;
+  return neighbour_backward_workspace(N, P1, P2, K, INT32_MAX);
 }
 
 int32_t mr_ball_query_backward(const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2,
@@ -292,22 +271,8 @@ int32_t mr_ball_query_backward(const float* p1, const float* p2, int64_t N, int6
                                void* stream) {
   if (int rc = check_sizes("ball query backward", N, P1, P2)) return rc;
   if (K < 1) return set_err(MR_EINVAL, "ball query backward: K must be >= 1");
-  if (!p1 || !p2 || !idx || !grad_dists || !grad_p1 || !grad_p2 || !ws)
-    return set_err(MR_EINVAL, "ball query backward: NULL pointer");
-  const FixWS w = carve_fix(ws, 3 * N * P2);
-  if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "ball query backward workspace too small");
-  const hipStream_t st = (hipStream_t)stream;
-  const int64_t words = (int64_t)(w.bytes / sizeof(u64));  // the carve ends on a multiple of 256 B
-  if (int rc = launch(KID_NONE, "k_zero_words", k_zero_words, (unsigned)ceil_div(words, MRK_TBLOCK), MRK_TBLOCK, 0, st,
-                      (u64*)ws, words))
-    return rc;
-  const dim3 grid((unsigned)ceil_div(P1, MRK_TBLOCK), (unsigned)N);
-  const int k = K;
-  if (int rc = launch(KID_NONE, "k_knn_bwd", k_knn_bwd<2>, grid, MRK_TBLOCK, 0, st, p1, p2, P1, P2, lengths1, lengths2,
-                      k, idx, grad_dists, grad_p1, w.fix, w.rem))
-    return rc;
-  return launch(KID_NONE, "k_knn_bwd_p2", k_knn_bwd_p2, (unsigned)ceil_div(3 * N * P2, MRK_TBLOCK), MRK_TBLOCK, 0, st,
-                (const u64*)w.fix, (const float*)w.rem, 3 * N * P2, grad_p2);
+  return neighbour_backward("ball query backward", 2, K, p1, p2, N, P1, P2, lengths1, lengths2, idx, grad_dists,
+                            grad_p1, grad_p2, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

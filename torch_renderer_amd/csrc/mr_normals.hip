@@ -2,9 +2,9 @@
 // estimate_pointcloud_normals, 2 <= K <= 64): mr_point_frames / mr_point_frames_geometry / mr_symmetric_eig3_host of
 // include/mi355r.h.
 //
-//   k_frames        k_knn's scan (mr_knn.h) of a cloud against itself: a workgroup owns a tile of queries (Q per
-//                   thread) and keeps every query's KB smallest (distance, index) keys ascending in registers, KB the
-//                   bucket 8, 16, 32, 64 of K and Q = 4, 2, 1, 1. With splits == 1 the same thread then runs
+//   k_frames        k_knn's scan (mr_knn.h's knn_scan) of a cloud against itself: a workgroup owns a tile of queries
+//                   (Q per thread) and keeps every query's KB smallest (distance, index) keys ascending in registers,
+//                   KB the bucket 8, 16, 32, 64 of K and Q = 4, 2, 1, 1. With splits == 1 the same thread then runs
 //                   frames_epilogue on its list: it gathers the K neighbours' coordinates three times (mean of
 //                   d_k = p_k - p_i; covariance of d_k - mean; the projections of the sign step), solves the 3x3
 //                   with sym_eig3 and stores. No index or neighbour tensor goes to memory on this path.
@@ -211,6 +211,10 @@ __device__ __forceinline__ void frames_epilogue(const u64 (&L)[KB], bool ok, int
 }
 
 // grid (query tiles * splits, N). part != NULL: (N, P, splits, K) keys for k_frames_merge; else the frames themselves.
+// The tile prologue and the store of the partial lists stay written out here, beside mr_knn.h's scan_tile and
+// knn_store_keys, which k_knn uses: with the helpers KB = 64 ran 4.6 % slower (1 x 20,000, K = 50: 6,944 / 6,992 us
+// against 6,680 / 6,643; 300 x 2,000: 13,823 / 13,833 against 13,192 / 13,229) and KB = 16 compiled to 129 VGPRs for
+// 128, three waves per SIMD for four (profiles/neighbour_fold_ab.txt, neighbour_fold_codeobj.txt).
 template <int KB, int Q>
 __global__ void __launch_bounds__(MRN_BLOCK) k_frames(const float* __restrict__ pts, int64_t P,
                                                       const int64_t* __restrict__ lens, int K, int flags, int splits,
@@ -297,17 +301,13 @@ int32_t mr_point_frames_geometry(int64_t N, int64_t P, int32_t K, int32_t* bucke
   if (int rc = check_frames("point frames geometry", N, P, K)) return rc;
   const KnnGeom g = knn_geom(N, P, P, K, MRF_MIN_BUCKET);
   if (bucket) *bucket = g.kb;
-  if (queries_per_group) *queries_per_group = MRN_BLOCK * g.q;
-  if (splits) *splits = g.splits;
-  if (lds_chunk) *lds_chunk = g.chunk;
+  geom_out(g, queries_per_group, splits, lds_chunk);
   return MR_OK;
 }
 
 size_t mr_point_frames_workspace(int64_t N, int64_t P, int32_t K) {
   if (!frames_args_ok(N, P, K)) return 0;
-  Carver c(nullptr);
-  c.take<u64>(knn_part_bytes(N, P, K, knn_geom(N, P, P, K, MRF_MIN_BUCKET)) / sizeof(u64) + 1);  // never 0: 0 means out of range
-  return c.off;
+  return knn_ws_bytes(N, P, K, knn_geom(N, P, P, K, MRF_MIN_BUCKET));
 }
 
 int32_t mr_point_frames(const float* points, int64_t N, int64_t P, const int64_t* lengths, int32_t K, int32_t flags,

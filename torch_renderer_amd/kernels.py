@@ -196,8 +196,7 @@ class MeshShapePriors(torch.autograd.Function):
             raise RuntimeError("mesh priors: faces and vertices live on different devices")
         want = bool(ctx.needs_input_grad[0])
         out = torch.empty(3, device=v.device)
-        wsb = _ws_size(L.mr_mesh_priors_workspace, topo.V, topo.E, topo.P)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=v.device)
+        ws, wsb = _workspace(L.mr_mesh_priors_workspace, v.device, topo.V, topo.E, topo.P)
         check(L.mr_mesh_priors_forward(ptr(v), topo.V, ptr(topo.edges), ptr(topo.edge_w), topo.E, ptr(topo.nbr_ptr),
                                        ptr(topo.nbr), ptr(topo.vert_w), ptr(topo.pairs), ptr(topo.pair_w), topo.P,
                                        float(target_length), int(terms), int(want), ptr(out), ptr(ws), wsb,
@@ -259,8 +258,7 @@ def nearest_points(x, y, x_lengths=None, y_lengths=None, norm=2):
     dev = xf.device
     dx, ix = torch.empty((N, P1), device=dev), torch.empty((N, P1), dtype=torch.int32, device=dev)
     dy, iy = torch.empty((N, P2), device=dev), torch.empty((N, P2), dtype=torch.int32, device=dev)
-    wsb = _ws_size(L.mr_nearest_points_workspace, N, P1, P2)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    ws, wsb = _workspace(L.mr_nearest_points_workspace, dev, N, P1, P2)
     check(L.mr_nearest_points(ptr(xf), ptr(yf), N, P1, P2, ptr(xl), ptr(yl), int(norm), ptr(dx), ptr(ix), ptr(dy),
                               ptr(iy), ptr(ws), wsb, _lib.stream_handle(dev)))
     return dx, ix, dy, iy
@@ -286,8 +284,7 @@ class ChamferDistance(torch.autograd.Function):
         ix = torch.empty((N, P1), dtype=torch.int32, device=dev) if want else None
         iy = torch.empty((N, P2), dtype=torch.int32, device=dev) if want and not single else None
         coef = torch.empty((2, N), device=dev) if want else None
-        wsb = _ws_size(L.mr_chamfer_workspace, N, P1, P2)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        ws, wsb = _workspace(L.mr_chamfer_workspace, dev, N, P1, P2)
         check(L.mr_chamfer_forward(ptr(xf), ptr(yf), N, P1, P2, ptr(xl), ptr(yl), ptr(w), int(norm), int(flags),
                                    ptr(ix), ptr(iy), ptr(coef), ptr(out), ptr(ws), wsb, _lib.stream_handle(dev)))
         ctx.set_materialize_grads(False)
@@ -307,11 +304,64 @@ class ChamferDistance(torch.autograd.Function):
         L = _lib.load()
         N, P1, P2 = xf.shape[0], xf.shape[1], yf.shape[1]
         gx, gy = torch.empty_like(xf), torch.empty_like(yf)
-        wsb = _ws_size(L.mr_chamfer_backward_workspace, N, P1, P2)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=xf.device)
+        ws, wsb = _workspace(L.mr_chamfer_backward_workspace, xf.device, N, P1, P2)
         check(L.mr_chamfer_backward(ptr(xf), ptr(yf), N, P1, P2, norm, flags, ptr(ix), ptr(iy), ptr(coef), ptr(g),
                                     ptr(gx), ptr(gy), ptr(ws), wsb, _lib.stream_handle(xf.device)))
         return gx.to(xdt), gy.to(ydt), None, None, None, None, None
+
+
+# --------------------------------------------------------------------------- neighbour searches (csrc/mr_knn.h)
+def _geometry(fn, n_out, *args):
+    """The ``n_out`` int32 values a host-only ``*_geometry`` entry point reports for ``args``."""
+    out = [ctypes.c_int32() for _ in range(n_out)]
+    check(fn(*args, *(ctypes.byref(o) for o in out)))
+    return tuple(o.value for o in out)
+
+
+def _neighbour_forward(workspace, launch, scalar, p1f, p2f, l1, l2, N, P1, P2, K):
+    """(dists, idx), both (N,P1,K), of mr_knn_points or mr_ball_query: the two entry points take the same arguments
+    but for one ``scalar``, the norm or the radius."""
+    dev = p1f.device
+    dists = torch.empty((N, P1, K), device=dev)
+    idx = torch.empty((N, P1, K), dtype=torch.int32, device=dev)
+    ws, wsb = _workspace(workspace, dev, N, P1, P2, K)
+    check(launch(ptr(p1f), ptr(p2f), N, P1, P2, ptr(l1), ptr(l2), scalar, K, ptr(dists), ptr(idx), ptr(ws), wsb,
+                 _lib.stream_handle(dev)))
+    return dists, idx
+
+
+class _NeighbourDists(torch.autograd.Function):
+    """What KnnPoints and BallQuery are: a search ``_search(p1, p2, lengths1, lengths2, K, x)`` -> (dists, idx, the
+    float32 clouds and int64 lengths it ran on, the checked K) with the gradient of ``dists`` w.r.t. p1 and p2 (``idx``
+    is not differentiable): three launches backward and no memset, the many-to-one p2 side summed in fixed point, by
+    the ``_backward`` entry point, which takes ``x`` as its norm if ``_pass_norm``."""
+
+    @staticmethod
+    def forward(ctx, p1, p2, lengths1, lengths2, K, x):
+        cls = ctx._forward_cls  # the subclass that was applied
+        dists, idx, (p1f, p2f, l1, l2), K = cls._search(p1, p2, lengths1, lengths2, K, x)
+        ctx.mark_non_differentiable(idx)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(p1f, p2f, idx, l1, l2)
+        ctx.args = (K, (int(x),) if cls._pass_norm else (), p1.dtype, p2.dtype)
+        return dists, idx
+
+    @staticmethod
+    def backward(ctx, g, _g_idx):
+        if g is None:
+            return (None,) * 6
+        p1f, p2f, idx, l1, l2 = ctx.saved_tensors
+        K, norm, dt1, dt2 = ctx.args
+        g = g.detach().float().contiguous()
+        _require_cuda(g)
+        L = _lib.load()
+        name = ctx._forward_cls._backward
+        N, P1, P2 = p1f.shape[0], p1f.shape[1], p2f.shape[1]
+        g1, g2 = torch.empty_like(p1f), torch.empty_like(p2f)
+        ws, wsb = _workspace(getattr(L, name + "_workspace"), p1f.device, N, P1, P2, K)
+        check(getattr(L, name)(ptr(p1f), ptr(p2f), N, P1, P2, ptr(l1), ptr(l2), *norm, K, ptr(idx), ptr(g), ptr(g1),
+                               ptr(g2), ptr(ws), wsb, _lib.stream_handle(p1f.device)))
+        return g1.to(dt1), g2.to(dt2), None, None, None, None
 
 
 # --------------------------------------------------------------------------- K nearest neighbours (csrc/mr_knn.hip)
@@ -329,21 +379,16 @@ def _knn_k(K):
 
 def knn_geometry(N, P1, P2, K):
     """(queries_per_group, splits, lds_chunk) of the launch mr_knn_points makes for these shapes (host only)."""
-    out = [ctypes.c_int32() for _ in range(3)]
-    check(_lib.load().mr_knn_geometry(int(N), int(P1), int(P2), _knn_k(K), *(ctypes.byref(o) for o in out)))
-    return tuple(o.value for o in out)
+    return _geometry(_lib.load().mr_knn_geometry, 3, int(N), int(P1), int(P2), _knn_k(K))
 
 
-def _knn_forward(p1f, p2f, l1, l2, N, P1, P2, K, norm):
+def _knn_search(p1, p2, lengths1, lengths2, K, norm):
+    K = _knn_k(K)
+    p1f, p2f, l1, l2, N, P1, P2 = _cloud_args(p1, p2, lengths1, lengths2, norm)
     L = _lib.load()
-    dev = p1f.device
-    dists = torch.empty((N, P1, K), device=dev)
-    idx = torch.empty((N, P1, K), dtype=torch.int32, device=dev)
-    wsb = _ws_size(L.mr_knn_points_workspace, N, P1, P2, K)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    check(L.mr_knn_points(ptr(p1f), ptr(p2f), N, P1, P2, ptr(l1), ptr(l2), int(norm), K, ptr(dists), ptr(idx), ptr(ws),
-                          wsb, _lib.stream_handle(dev)))
-    return dists, idx
+    dists, idx = _neighbour_forward(L.mr_knn_points_workspace, L.mr_knn_points, int(norm), p1f, p2f, l1, l2, N, P1, P2,
+                                    K)
+    return dists, idx, (p1f, p2f, l1, l2), K
 
 
 def knn_points(p1, p2, lengths1=None, lengths2=None, K=1, norm=2):
@@ -351,42 +396,13 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, K=1, norm=2):
     p2[n, :lengths2[n]], ascending by (distance, index), with nearest_points' distance; equal distances take the
     lower index. Slots k >= min(K, lengths2[n]) and rows past lengths1[n] are 0 / -1. 1 <= K <= 32. No autograd; one
     launch, or a scan and a merge when the shapes alone cannot fill the chip (mr_knn_points)."""
-    K = _knn_k(K)
-    p1f, p2f, l1, l2, N, P1, P2 = _cloud_args(p1, p2, lengths1, lengths2, norm)
-    return _knn_forward(p1f, p2f, l1, l2, N, P1, P2, K, norm)
+    return _knn_search(p1, p2, lengths1, lengths2, K, norm)[:2]
 
 
-class KnnPoints(torch.autograd.Function):
-    """knn_points with the gradient of ``dists`` w.r.t. p1 and p2 (``idx`` is not differentiable): one memset and two
-    launches backward, the many-to-one p2 side summed in fixed point (mr_knn_points_backward)."""
-
-    @staticmethod
-    def forward(ctx, p1, p2, lengths1, lengths2, K, norm):
-        K = _knn_k(K)
-        p1f, p2f, l1, l2, N, P1, P2 = _cloud_args(p1, p2, lengths1, lengths2, norm)
-        dists, idx = _knn_forward(p1f, p2f, l1, l2, N, P1, P2, K, norm)
-        ctx.mark_non_differentiable(idx)
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(p1f, p2f, idx, l1, l2)
-        ctx.args = (K, int(norm), p1.dtype, p2.dtype)
-        return dists, idx
-
-    @staticmethod
-    def backward(ctx, g, _g_idx):
-        if g is None:
-            return (None,) * 6
-        p1f, p2f, idx, l1, l2 = ctx.saved_tensors
-        K, norm, dt1, dt2 = ctx.args
-        g = g.detach().float().contiguous()
-        _require_cuda(g)
-        L = _lib.load()
-        N, P1, P2 = p1f.shape[0], p1f.shape[1], p2f.shape[1]
-        g1, g2 = torch.empty_like(p1f), torch.empty_like(p2f)
-        wsb = _ws_size(L.mr_knn_points_backward_workspace, N, P1, P2, K)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=p1f.device)
-        check(L.mr_knn_points_backward(ptr(p1f), ptr(p2f), N, P1, P2, ptr(l1), ptr(l2), norm, K, ptr(idx), ptr(g),
-                                       ptr(g1), ptr(g2), ptr(ws), wsb, _lib.stream_handle(p1f.device)))
-        return g1.to(dt1), g2.to(dt2), None, None, None, None
+class KnnPoints(_NeighbourDists):
+    """knn_points with the gradient of ``dists`` w.r.t. p1 and p2 (``idx`` is not differentiable): three launches
+    backward and no memset, the many-to-one p2 side summed in fixed point (mr_knn_points_backward)."""
+    _search, _backward, _pass_norm = staticmethod(_knn_search), "mr_knn_points_backward", True
 
 
 # --------------------------------------------------------------------------- radius neighbourhoods (csrc/mr_ballquery.hip)
@@ -401,21 +417,16 @@ def _ball_args(K, radius):
 
 def ball_query_geometry(N, P1, P2, K):
     """(queries_per_group, splits, lds_chunk) of the launches mr_ball_query makes for these shapes (host only)."""
-    out = [ctypes.c_int32() for _ in range(3)]
-    check(_lib.load().mr_ball_query_geometry(int(N), int(P1), int(P2), int(K), *(ctypes.byref(o) for o in out)))
-    return tuple(o.value for o in out)
+    return _geometry(_lib.load().mr_ball_query_geometry, 3, int(N), int(P1), int(P2), int(K))
 
 
-def _ball_forward(p1f, p2f, l1, l2, N, P1, P2, K, radius):
+def _ball_search(p1, p2, lengths1, lengths2, K, radius):
+    K, radius = _ball_args(K, radius)
+    p1f, p2f, l1, l2, N, P1, P2 = _cloud_args(p1, p2, lengths1, lengths2, 2)
     L = _lib.load()
-    dev = p1f.device
-    dists = torch.empty((N, P1, K), device=dev)
-    idx = torch.empty((N, P1, K), dtype=torch.int32, device=dev)
-    wsb = _ws_size(L.mr_ball_query_workspace, N, P1, P2, K)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    check(L.mr_ball_query(ptr(p1f), ptr(p2f), N, P1, P2, ptr(l1), ptr(l2), radius, K, ptr(dists), ptr(idx), ptr(ws),
-                          wsb, _lib.stream_handle(dev)))
-    return dists, idx
+    dists, idx = _neighbour_forward(L.mr_ball_query_workspace, L.mr_ball_query, radius, p1f, p2f, l1, l2, N, P1, P2,
+                                    K)
+    return dists, idx, (p1f, p2f, l1, l2), K
 
 
 def ball_query(p1, p2, lengths1=None, lengths2=None, K=500, radius=0.2):
@@ -423,42 +434,13 @@ def ball_query(p1, p2, lengths1=None, lengths2=None, K=500, radius=0.2):
     p2[n, :lengths2[n]], in index order, whose float32 squared distance (nearest_points') is < float32(radius)^2;
     dists holds those distances, unsorted. Free slots and rows past lengths1[n] are 0 / -1. Any K >= 1. No autograd;
     one launch, or a counting and a writing pass when the shapes alone cannot fill the chip (mr_ball_query)."""
-    K, radius = _ball_args(K, radius)
-    p1f, p2f, l1, l2, N, P1, P2 = _cloud_args(p1, p2, lengths1, lengths2, 2)
-    return _ball_forward(p1f, p2f, l1, l2, N, P1, P2, K, radius)
+    return _ball_search(p1, p2, lengths1, lengths2, K, radius)[:2]
 
 
-class BallQuery(torch.autograd.Function):
+class BallQuery(_NeighbourDists):
     """ball_query with the gradient of ``dists`` w.r.t. p1 and p2 (``idx`` is not differentiable): three launches
     backward and no memset, the many-to-one p2 side summed in fixed point (mr_ball_query_backward)."""
-
-    @staticmethod
-    def forward(ctx, p1, p2, lengths1, lengths2, K, radius):
-        K, radius = _ball_args(K, radius)
-        p1f, p2f, l1, l2, N, P1, P2 = _cloud_args(p1, p2, lengths1, lengths2, 2)
-        dists, idx = _ball_forward(p1f, p2f, l1, l2, N, P1, P2, K, radius)
-        ctx.mark_non_differentiable(idx)
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(p1f, p2f, idx, l1, l2)
-        ctx.args = (K, p1.dtype, p2.dtype)
-        return dists, idx
-
-    @staticmethod
-    def backward(ctx, g, _g_idx):
-        if g is None:
-            return (None,) * 6
-        p1f, p2f, idx, l1, l2 = ctx.saved_tensors
-        K, dt1, dt2 = ctx.args
-        g = g.detach().float().contiguous()
-        _require_cuda(g)
-        L = _lib.load()
-        N, P1, P2 = p1f.shape[0], p1f.shape[1], p2f.shape[1]
-        g1, g2 = torch.empty_like(p1f), torch.empty_like(p2f)
-        wsb = _ws_size(L.mr_ball_query_backward_workspace, N, P1, P2, K)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=p1f.device)
-        check(L.mr_ball_query_backward(ptr(p1f), ptr(p2f), N, P1, P2, ptr(l1), ptr(l2), K, ptr(idx), ptr(g), ptr(g1),
-                                       ptr(g2), ptr(ws), wsb, _lib.stream_handle(p1f.device)))
-        return g1.to(dt1), g2.to(dt2), None, None, None, None
+    _search, _backward, _pass_norm = staticmethod(_ball_search), "mr_ball_query_backward", False
 
 
 # --------------------------------------------------------------------------- farthest points (csrc/mr_fps.hip)
@@ -466,9 +448,8 @@ def farthest_geometry(N, P, Kmax):
     """(threads, points_per_thread, streamed) of the launch mr_farthest_points makes for these shapes (host only):
     the workgroup size, the points a thread keeps in registers (the bucket 1, 2, 4, ..., 32; for a streamed cloud
     the points a thread walks every round), and whether the cloud is too large for the registers."""
-    out = [ctypes.c_int32() for _ in range(3)]
-    check(_lib.load().mr_farthest_points_geometry(int(N), int(P), int(Kmax), *(ctypes.byref(o) for o in out)))
-    return out[0].value, out[1].value, bool(out[2].value)
+    threads, per_thread, streamed = _geometry(_lib.load().mr_farthest_points_geometry, 3, int(N), int(P), int(Kmax))
+    return threads, per_thread, bool(streamed)
 
 
 def _farthest_args(points, lengths, K, start_idx, Kmax):
@@ -510,10 +491,8 @@ def farthest_points(points, lengths=None, K=50, start_idx=None, Kmax=None):
     dev = pf.device
     idx = torch.empty((N, Kmax), dtype=torch.int32, device=dev)
     pts = torch.empty((N, Kmax, 3), device=dev)
-    wsb = _ws_size(L.mr_farthest_points_workspace, N, P, Kmax)
-    if wsb == 0:
-        raise NotImplementedError("mi355r: farthest points: clouds too large for 32-bit point ids")
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    ws, wsb = _workspace(L.mr_farthest_points_workspace, dev, N, P, Kmax,
+                         what="mi355r: farthest points: clouds too large for 32-bit point ids")
     check(L.mr_farthest_points(ptr(pf), N, P, ptr(l), ptr(kper), Kmax, ptr(st), ptr(idx), ptr(pts), ptr(ws), wsb,
                                _lib.stream_handle(dev)))
     return idx, pts
@@ -566,9 +545,7 @@ def _frames_k(K, P):
 
 def frames_geometry(N, P, K):
     """(bucket, queries_per_group, splits, lds_chunk) of the launch mr_point_frames makes for these shapes (host only)."""
-    out = [ctypes.c_int32() for _ in range(4)]
-    check(_lib.load().mr_point_frames_geometry(int(N), int(P), _frames_k(K, int(P)), *(ctypes.byref(o) for o in out)))
-    return tuple(o.value for o in out)
+    return _geometry(_lib.load().mr_point_frames_geometry, 4, int(N), int(P), _frames_k(K, int(P)))
 
 
 def symmetric_eig3_host(cov):
@@ -610,8 +587,7 @@ def point_frames(points, lengths=None, K=50, disambiguate=True, return_cov=False
     dev = pf.device
     cur, frm = torch.empty((N, P, 3), device=dev), torch.empty((N, P, 3, 3), device=dev)
     cov = torch.empty((N, P, 6), device=dev) if return_cov else None
-    wsb = _ws_size(L.mr_point_frames_workspace, N, P, K)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    ws, wsb = _workspace(L.mr_point_frames_workspace, dev, N, P, K)
     check(L.mr_point_frames(ptr(pf), N, P, ptr(l), K, _lib.MR_FRAMES_DISAMBIGUATE if disambiguate else 0, ptr(cur),
                             ptr(frm), ptr(cov), ptr(ws), wsb, _lib.stream_handle(dev)))
     return (cur, frm, cov) if return_cov else (cur, frm)
@@ -660,10 +636,9 @@ def _posed_chamfer_launch(xf, yf, rts, norm, flags, want_idx, want_grad):
     ix = torch.empty((S, P1), dtype=torch.int32, device=dev) if want_idx else None
     iy = torch.empty((S, P2), dtype=torch.int32, device=dev) if want_idx and not single else None
     pg = torch.empty((S, 13), device=dev) if want_grad else None
-    wsb = _ws_size(L.mr_posed_chamfer_workspace, S, P1, P2)
-    if wsb == 0:
-        raise NotImplementedError("mi355r: posed chamfer: more than 65535 poses or clouds too large for 32-bit point ids")
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    ws, wsb = _workspace(L.mr_posed_chamfer_workspace, dev, S, P1, P2,
+                         what="mi355r: posed chamfer: more than 65535 poses or clouds too large for 32-bit point "
+                              "ids")
     check(L.mr_posed_chamfer(ptr(xf), ptr(yf), P1, P2, ptr(rts), S, int(norm), int(flags), ptr(out), ptr(ix), ptr(iy),
                              ptr(pg), ptr(ws), wsb, _lib.stream_handle(dev)))
     return out, ix, iy, pg
@@ -798,11 +773,9 @@ def _pm_nearest(points, verts, batch, min_triangle_area, want=(True, True, True,
     P, T = pf.shape[0], batch.faces.shape[0]
     outs = [torch.empty(n, dtype=dt, device=dev) if w else None
             for n, dt, w in zip((P, P, T, T), (torch.float32, torch.int32, torch.float32, torch.int32), want)]
-    wsb = _ws_size(L.mr_point_face_nearest_workspace, batch.N, P, T)
-    if wsb == 0:
-        raise NotImplementedError("mi355r: point-face nearest: more than 65535 meshes or a batch too large for "
-                                  "32-bit indices")
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    ws, wsb = _workspace(L.mr_point_face_nearest_workspace, dev, batch.N, P, T,
+                         what="mi355r: point-face nearest: more than 65535 meshes or a batch too large for 32-bit "
+                              "indices")
     check(L.mr_point_face_nearest(*args, ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), ptr(outs[3]), ptr(ws), wsb,
                                   _lib.stream_handle(dev)))
     return outs, keep
@@ -828,8 +801,7 @@ def _pm_backward(keep, batch_args, idx_p, idx_f, coef, g, gdp, gdf):
     pf, vf = keep[0], keep[1]
     L = _lib.load()
     gp, gv = torch.empty_like(pf), torch.empty_like(vf)
-    wsb = _ws_size(L.mr_point_mesh_face_backward_workspace, pf.shape[0], vf.shape[0])
-    ws = torch.empty(wsb, dtype=torch.uint8, device=pf.device)
+    ws, wsb = _workspace(L.mr_point_mesh_face_backward_workspace, pf.device, pf.shape[0], vf.shape[0])
     check(L.mr_point_mesh_face_backward(*batch_args, ptr(idx_p), ptr(idx_f), ptr(coef), ptr(g), ptr(gdp), ptr(gdf),
                                         ptr(gp), ptr(gv), ptr(ws), wsb, _lib.stream_handle(pf.device)))
     return gp, gv
@@ -852,11 +824,9 @@ class PointMeshFaceDistance(torch.autograd.Function):
         ip = torch.empty(P, dtype=torch.int32, device=dev) if want else None
         it = torch.empty(T, dtype=torch.int32, device=dev) if want else None
         coef = torch.empty((2, N), device=dev) if want else None
-        wsb = _ws_size(L.mr_point_mesh_face_workspace, N, P, T)
-        if wsb == 0:
-            raise NotImplementedError("mi355r: point-mesh face distance: more than 65535 meshes or a batch too large "
-                                      "for 32-bit indices")
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        ws, wsb = _workspace(L.mr_point_mesh_face_workspace, dev, N, P, T,
+                             what="mi355r: point-mesh face distance: more than 65535 meshes or a batch too large "
+                                  "for 32-bit indices")
         check(L.mr_point_mesh_face_forward(*args, ptr(ip), ptr(it), ptr(coef), ptr(out), ptr(ws), wsb,
                                            _lib.stream_handle(dev)))
         ctx.set_materialize_grads(False)
@@ -927,8 +897,7 @@ def points_alignment(x, y, lengths=None, weights=None, flags=0, eps=1e-9):
     L = _lib.load()
     dev = xf.device
     rts = torch.empty((N, 13), device=dev)
-    wsb = _ws_size(L.mr_points_alignment_workspace, N, P)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    ws, wsb = _workspace(L.mr_points_alignment_workspace, dev, N, P)
     check(L.mr_points_alignment(ptr(xf), ptr(yf), N, P, ptr(xl), ptr(w), int(flags), float(eps), ptr(rts), ptr(ws),
                                 wsb, _lib.stream_handle(dev)))
     return rts
@@ -958,8 +927,7 @@ def _icp_loop(xf, xl, N, P1, P2, init, max_iterations, status_batch, workspace_q
     max_iterations = int(max_iterations)
     rts = torch.empty((N, 13), device=dev)
     status = torch.empty(2, dtype=torch.int32, device=dev)
-    wsb = _ws_size(workspace_query, N, P1, P2)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    ws, wsb = _workspace(workspace_query, dev, N, P1, P2)
     check(L.mr_icp_init(ptr(xf), N, P1, P2, ptr(xl), ptr(R0), ptr(T0), ptr(s0), ptr(rts), ptr(status), ptr(ws), wsb, st))
     done, iters, rmse = 0, 0, None
     hist = torch.empty((max(max_iterations, 0), N, 13), device=dev)
@@ -1066,8 +1034,7 @@ class SamplePoints(torch.autograd.Function):
         _require_cuda(g)
         L = _lib.load()
         gv = torch.empty((V, 3), device=g.device)
-        wsb = _ws_size(L.mr_sample_points_backward_workspace, V)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=g.device)
+        ws, wsb = _workspace(L.mr_sample_points_backward_workspace, g.device, V)
         check(L.mr_sample_points_backward(V, ptr(f), f.shape[0], ptr(fi), ptr(uvf), fi.numel(), ptr(g), ptr(gv),
                                           ptr(ws), wsb, _lib.stream_handle(g.device)))
         return gv.to(dtype), None, None, None
@@ -1369,6 +1336,15 @@ def _ws_size(fn, *args):
             _WS_CACHE.clear()
         v = _WS_CACHE[k] = int(fn(*args))
     return v
+
+
+def _workspace(fn, device, *shape, what=None):
+    """(ws, wsb): a uint8 workspace of the ``fn(*shape)`` bytes on ``device``, and that size. With ``what``, a size of
+    0 (the library's answer to shapes it does not take) raises NotImplementedError(what)."""
+    wsb = _ws_size(fn, *shape)
+    if what is not None and wsb == 0:
+        raise NotImplementedError(what)
+    return torch.empty(wsb, dtype=torch.uint8, device=device), wsb
 
 
 @dataclass
@@ -1736,8 +1712,7 @@ def rasterize_points_bwd(points_ndc, first, idx, gz, gd, idx_base=None):
     N, H, W, K = idx.shape
     g = torch.empty_like(p)
     gz, gd = (None if t is None else t.float().contiguous() for t in (gz, gd))
-    wsb = _ws_size(L.mr_rasterize_points_backward_workspace, p.shape[0])
-    ws = torch.empty(wsb, dtype=torch.uint8, device=p.device)
+    ws, wsb = _workspace(L.mr_rasterize_points_backward_workspace, p.device, p.shape[0])
     check(L.mr_rasterize_points_backward(ptr(p), ptr(first), ptr(idx_base), N, p.shape[0], H, W, K,
                                          ptr(idx.contiguous()), ptr(gz), ptr(gd), ptr(g), ptr(ws), wsb,
                                          _lib.stream_handle(p.device)))
@@ -1796,8 +1771,7 @@ class ProjectPoints(torch.autograd.Function):
         N = views.shape[0]
         gp = torch.empty_like(p)
         gviews = torch.empty((N, 12), device=p.device)
-        wsb = _ws_size(L.mr_project_points_backward_workspace, p.shape[0])
-        ws = torch.empty(wsb, dtype=torch.uint8, device=p.device)
+        ws, wsb = _workspace(L.mr_project_points_backward_workspace, p.device, p.shape[0])
         check(L.mr_project_points_backward(ptr(p), ptr(src_first), ptr(dst_first), ptr(count), N, p.shape[0], ptr(views),
                                            ptr(g.float().contiguous()), ptr(gp), ptr(gviews), ptr(ws), wsb,
                                            _lib.stream_handle(p.device)))
@@ -1841,8 +1815,7 @@ class CompositePoints(torch.autograd.Function):
         P, C = f.shape
         gv = torch.empty_like(v)
         gf = torch.empty_like(f)
-        wsb = _ws_size(L.mr_composite_points_backward_workspace, P, C)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=f.device)
+        ws, wsb = _workspace(L.mr_composite_points_backward_workspace, f.device, P, C)
         check(L.mr_composite_points_backward(ptr(ix), ptr(v), ptr(f), *ctx.sizes, ptr(e(rpp)), rpp.shape[0],
                                              ptr(e(feat_sub)), ptr(e(background)), ptr(g.float().contiguous()),
                                              ptr(gv), ptr(gf), ptr(ws), wsb, _lib.stream_handle(f.device)))
