@@ -795,6 +795,54 @@ int32_t mr_ball_query_backward(const float* p1, const float* p2, int64_t N, int6
                                const float* grad_dists, float* grad_p1, float* grad_p2, void* ws, size_t ws_bytes,
                                void* stream);
 
+/* ICP onto a mesh surface: a third estimator on the loop of mr_icp_iterate, rigid (s stays what mr_icp_init set),
+ * the point-to-plane step above against the closest points of the meshes' surfaces. x (N,P1,3) with x_lengths; the
+ * packed mesh arguments are mr_point_face_nearest's (above): verts (V,3), faces (T,3) int32 over packed vertex ids,
+ * faces_first / faces_count (N) int64 device arrays, max_faces a host-side bound of the counts. Meshes may share
+ * faces (equal faces_first): the records are per packed face. mr_icp_init (with any P2 >= 1) and mr_icp_transform
+ * are used as they are, on a workspace of mr_icp_mesh_workspace bytes (it begins with mr_icp_plane_workspace's
+ * layout). mr_icp_mesh_prepare, once after mr_icp_init and before the first iteration, writes every packed face's
+ * triangle record for min_triangle_area into the workspace; the mesh must not change until the registration ends.
+ * max_dist2 is the float32 square of the maximum correspondence distance, rounded once, or +inf.
+ * Per cloud n with L1 points, mesh n with T_n faces, (R, T, s) = rts, every iteration:
+ *  1. Search. p_i = s (x_i R) + T in float32 (the transform code above), i < L1; f(i) the face of mesh n with the
+ *     smallest d(p_i, tri), d exactly mr_point_face_nearest's distance for min_triangle_area; the lowest face index
+ *     wins a tie; a face with a vertex id outside [0, V) is skipped.
+ *  2. Closest point and normal, in float32 without FMA, from the winner's pair: q_i = (b0 v0 + b1 v1) + b2 v2 per
+ *     component, b the closest point's barycentrics (those of the projection in the plane case; (1 - t, t) on the
+ *     winning edge and 0 at the third vertex otherwise). n_i is the triangle's unit normal if the plane branch
+ *     returned the distance; otherwise e = p_i - q_i, l = sqrtf((e0 e0 + e1 e1) + e2 e2), n_i = e / l if l > 1e-8,
+ *     else 0: the gradient direction of the distance function, which on a shared edge or vertex does not depend on
+ *     which of the tied faces won. A zero normal contributes nothing; the sign does not matter. A pair is valid iff
+ *     d <= max_dist2 (+inf: every pair); m counts the valid pairs.
+ *  3. Update. Steps 2 to 6 of mr_icp_plane_iterate, unchanged, with q_i and n_i in place of y_j and y_normals_j:
+ *     float64 A and b about c, lam = 1e-9 trace(A) / 6, the 6x6 Cholesky and Rodrigues, one rounding to float32 into
+ *     rts and slot status[1] of history, the point-to-plane rmse of this iteration's valid pairs under the new
+ *     transform, the relative-drop test. A cloud with m = 0 (an empty cloud, a mesh without a usable face, no pair
+ *     within the distance) keeps its transform bit for bit, reports rmse 0 and counts as done.
+ * Status words, idle kernels, batching of the status reads and the independence of the results from the batch size:
+ * as mr_icp_iterate. Four launches an iteration (the scan, closest points with the normal equations, the solve with
+ * the new residual, the status), no (P1,T) matrix, no host read; not differentiable.
+ * mr_icp_mesh_closest runs the scan and the closest-point code once on a prepared workspace, under rts (N,13) or,
+ * NULL, on x as it is: dist (N,P1) and face (N,P1; the index within the mesh) as mr_point_face_nearest's dist_p and
+ * idx_p (0 / -1 without a face or past the length; each may be NULL), q and normal (N,P1,3; zeros there).
+ * mr_icp_mesh_geometry (host only) reports the scan's launch geometry for a batch: the faces a workgroup stages
+ * (chunk, between min_chunk and max_chunk) and the workgroups per cloud; each output may be NULL. */
+size_t mr_icp_mesh_workspace(int64_t N, int64_t P1, int64_t T);
+int32_t mr_icp_mesh_geometry(int64_t N, int64_t P1, int64_t max_faces, int32_t* chunk, int32_t* min_chunk,
+                             int32_t* max_chunk, int64_t* groups);
+int32_t mr_icp_mesh_prepare(const float* verts, int64_t V, const int32_t* faces, int64_t T, const int64_t* faces_first,
+                            const int64_t* faces_count, int64_t max_faces, int64_t N, int64_t P1,
+                            float min_triangle_area, void* ws, size_t ws_bytes, void* stream);
+int32_t mr_icp_mesh_iterate(const float* x, int64_t N, int64_t P1, const int64_t* x_lengths, int64_t T,
+                            const int64_t* faces_first, const int64_t* faces_count, int64_t max_faces, float max_dist2,
+                            float relative_rmse_thr, int32_t max_iterations, int32_t iterations, float* rts,
+                            float* history, float* rmse, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+int32_t mr_icp_mesh_closest(const float* x, int64_t N, int64_t P1, const int64_t* x_lengths, const float* rts,
+                            int64_t T, const int64_t* faces_first, const int64_t* faces_count, int64_t max_faces,
+                            float* dist, int32_t* face, float* q, float* normal, void* ws, size_t ws_bytes,
+                            void* stream);
+
 /* Per-kernel timing with HIP events recorded on each launch's stream (bench.py).
  * enable=1 clears and starts collection; mr_timing_read synchronizes on the
  * recorded events and returns, per kernel id, launches and summed ms. */

@@ -198,6 +198,13 @@ _SIGS = [
     ("mr_icp_plane_iterate", _I32, [_VP, _VP, _VP, _I64, _I64, _I64, _VP, _VP, ctypes.c_float, ctypes.c_float, _I32,
                                     _I32, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     ("mr_icp_plane_solve_host", _I32, [_VP, _VP, _VP, _VP, _VP]),
+    ("mr_icp_mesh_workspace", _SZ, [_I64, _I64, _I64]),
+    ("mr_icp_mesh_geometry", _I32, [_I64, _I64, _I64, c_i32_p, c_i32_p, c_i32_p, ctypes.POINTER(ctypes.c_int64)]),
+    ("mr_icp_mesh_prepare", _I32, [_VP, _I64, _VP, _I64, _VP, _VP, _I64, _I64, _I64, ctypes.c_float, _VP, _SZ, _VP]),
+    ("mr_icp_mesh_iterate", _I32, [_VP, _I64, _I64, _VP, _I64, _VP, _VP, _I64, ctypes.c_float, ctypes.c_float, _I32,
+                                   _I32, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    ("mr_icp_mesh_closest", _I32, [_VP, _I64, _I64, _VP, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _SZ,
+                                   _VP]),
     ("mr_points_alignment_workspace", _SZ, [_I64, _I64]),
     ("mr_points_alignment", _I32, [_VP, _VP, _I64, _I64, _VP, _VP, _I32, ctypes.c_double, _VP, _VP, _SZ, _VP]),
     ("mr_sample_points_forward", _I32, [_VP, _I64, _VP, _I64, _VP, _VP, _I64, _VP, _VP]),

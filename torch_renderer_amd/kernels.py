@@ -913,8 +913,9 @@ def similarity_transform(x, rts):
     return out
 
 
-def _icp_loop(xf, xl, N, P1, P2, init, max_iterations, status_batch, workspace_query, iterate):
-    """What icp and icp_plane share: mr_icp_init on a workspace of ``workspace_query`` bytes, then
+def _icp_loop(xf, xl, N, P1, P2, init, max_iterations, status_batch, workspace_query, iterate, prepare=None):
+    """What icp, icp_plane and icp_mesh share: mr_icp_init on a workspace of ``workspace_query`` bytes,
+    ``prepare(ws, wsb, st)`` where the estimator has something to set up once, then
     ``iterate(k, rts, hist, rmse, status, ws, wsb, st)`` (the estimator's entry point for k more iterations) in batches
     of ``status_batch`` with one read of the two device status words after each, then mr_icp_transform."""
     L = _lib.load()
@@ -929,6 +930,8 @@ def _icp_loop(xf, xl, N, P1, P2, init, max_iterations, status_batch, workspace_q
     status = torch.empty(2, dtype=torch.int32, device=dev)
     ws, wsb = _workspace(workspace_query, dev, N, P1, P2)
     check(L.mr_icp_init(ptr(xf), N, P1, P2, ptr(xl), ptr(R0), ptr(T0), ptr(s0), ptr(rts), ptr(status), ptr(ws), wsb, st))
+    if prepare is not None:
+        check(prepare(ptr(ws), wsb, st))
     done, iters, rmse = 0, 0, None
     hist = torch.empty((max(max_iterations, 0), N, 13), device=dev)
     if max_iterations > 0:
@@ -982,6 +985,94 @@ def icp_plane(x, y, y_normals, x_lengths=None, y_lengths=None, init=None, max_it
                                       float(relative_rmse_thr), int(max_iterations), k, *state)
 
     return _icp_loop(xf, xl, N, P1, P2, init, max_iterations, status_batch, L.mr_icp_plane_workspace, iterate)
+
+
+def _icp_mesh_args(x, verts, batch, x_lengths, min_triangle_area, who):
+    """The checked inputs of a cloud-to-mesh call: contiguous float32 x (N,P1,3) and verts (V,3), the int64 lengths,
+    and the packed mesh arguments of the C ABI taken from ``batch`` (a PointMeshBatch, whose points_* fields are not
+    read here)."""
+    if x.dim() != 3:
+        raise ValueError(f"{who}: x must be an (N, P, D) tensor")
+    if verts.dim() != 2 or batch.faces.dim() != 2 or batch.faces.shape[1] != 3:
+        raise ValueError(f"{who}: verts (V, D) and faces (T, 3) are packed 2-D tensors")
+    if x.shape[2] != 3 or verts.shape[1] != 3:
+        raise NotImplementedError(f"{who}: only D = 3 is built")
+    N, P1 = int(x.shape[0]), int(x.shape[1])
+    if N < 1 or P1 < 1:
+        raise ValueError(f"{who}: N and P1 must be >= 1")
+    for t in (batch.faces_first, batch.faces_count) + (() if x_lengths is None else (x_lengths,)):
+        if tuple(t.shape) != (N,):
+            raise ValueError(f"{who}: faces_first, faces_count and the lengths must all be of shape (N,)")
+    if not float(min_triangle_area) >= 0.0:
+        raise ValueError(f"{who}: min_triangle_area must be >= 0")
+    _require_cuda(x, verts, batch.faces, batch.faces_first, batch.faces_count, x_lengths)
+    xf, vf = x.detach().float().contiguous(), verts.detach().float().contiguous()
+    faces = batch.faces.detach().to(torch.int32).contiguous()
+    ff, fc = (t.detach().to(torch.int64).contiguous() for t in (batch.faces_first, batch.faces_count))
+    xl = None if x_lengths is None else x_lengths.detach().to(torch.int64).contiguous()
+    T = int(faces.shape[0])
+    mesh = (T, ptr(ff), ptr(fc), min(max(int(batch.max_faces), 0), T))
+    return xf, vf, faces, xl, N, P1, mesh, (ff, fc)
+
+
+def _icp_mesh_prepare(L, vf, faces, mesh, N, P1, min_triangle_area):
+    T, ff, fc, max_faces = mesh
+    return lambda ws, wsb, st: L.mr_icp_mesh_prepare(ptr(vf), vf.shape[0], ptr(faces), T, ff, fc, max_faces, N, P1,
+                                                     float(min_triangle_area), ws, wsb, st)
+
+
+def icp_mesh(x, verts, batch, x_lengths=None, init=None, max_iterations=100, relative_rmse_thr=1e-6,
+             max_correspondence_distance=None, min_triangle_area=0.0, status_batch=None):
+    """The cloud-to-mesh ICP loop on the device (mr_icp_mesh_*, whose rule include/mi355r.h states), shaped like
+    ``icp_plane``: (converged, iterations run, rmse (N) or None, Xt (N,P1,3), rts (N,13), history (iterations,N,13)).
+    x (N,P1,3) with ``x_lengths``; cloud n registers onto mesh n of ``batch`` (a PointMeshBatch: faces (T,3) over the
+    packed ``verts`` (V,3), faces_first / faces_count (N), max_faces; meshes may share faces).
+    ``max_correspondence_distance`` d (None: no limit) reaches the kernels as float32(d) * float32(d) rounded once.
+    The triangle records are built once per call; the scale of ``init`` stays fixed. The results do not depend on
+    ``status_batch``."""
+    if max_correspondence_distance is not None and not float(max_correspondence_distance) >= 0.0:
+        raise ValueError("icp_mesh: max_correspondence_distance must be >= 0")
+    r2 = float("inf") if max_correspondence_distance is None else \
+        float(np.float32(max_correspondence_distance) * np.float32(max_correspondence_distance))
+    xf, vf, faces, xl, N, P1, mesh, keep = _icp_mesh_args(x, verts, batch, x_lengths, min_triangle_area, "icp_mesh")
+    L = _lib.load()
+    T = mesh[0]
+
+    def iterate(k, *state):
+        return L.mr_icp_mesh_iterate(ptr(xf), N, P1, ptr(xl), *mesh[:4], r2, float(relative_rmse_thr),
+                                     int(max_iterations), k, *state)
+
+    # the loop's third size is the face count here (at least 1: mr_icp_init wants a target; the workspace of one face
+    # serves a batch without faces)
+    return _icp_loop(xf, xl, N, P1, max(T, 1), init, max_iterations, status_batch, L.mr_icp_mesh_workspace, iterate,
+                     _icp_mesh_prepare(L, vf, faces, mesh, N, P1, min_triangle_area))
+
+
+def mesh_closest_points(x, verts, batch, rts=None, min_triangle_area=0.0):
+    """(dist (N,P1), face idx (N,P1) int32, q (N,P1,3), n (N,P1,3)) of x (N,P1,3) under ``rts`` (N,13; None: as it is)
+    against the meshes of ``batch``: the cloud-to-mesh loop's scan and closest-point code, run once
+    (mr_icp_mesh_prepare + mr_icp_mesh_closest). dist / idx are point_face_nearest's for the transformed points; q the
+    closest surface point; n the unit gradient direction of the distance function there (zero where p lies on the
+    surface); rows past ``batch.points_count`` (None: every row counts) or without a face get 0 / -1 / 0 / 0. For
+    tests and tools; nothing synchronises."""
+    xf, vf, faces, xl, N, P1, mesh, keep = _icp_mesh_args(x, verts, batch, batch.points_count, min_triangle_area,
+                                                          "mesh_closest_points")
+    L = _lib.load()
+    dev = xf.device
+    st = _lib.stream_handle(dev)
+    if rts is not None:
+        _require_cuda(rts)
+        if tuple(rts.shape) != (N, 13):
+            raise ValueError("mesh_closest_points: rts must be (N, 13)")
+        rts = rts.detach().float().contiguous()
+    ws, wsb = _workspace(L.mr_icp_mesh_workspace, dev, N, P1, mesh[0])
+    check(_icp_mesh_prepare(L, vf, faces, mesh, N, P1, min_triangle_area)(ptr(ws), wsb, st))
+    dist = torch.empty((N, P1), device=dev)
+    idx = torch.empty((N, P1), dtype=torch.int32, device=dev)
+    q, n = torch.empty((N, P1, 3), device=dev), torch.empty((N, P1, 3), device=dev)
+    check(L.mr_icp_mesh_closest(ptr(xf), N, P1, ptr(xl), ptr(rts), *mesh[:4], ptr(dist), ptr(idx), ptr(q), ptr(n),
+                                ptr(ws), wsb, st))
+    return dist, idx, q, n
 
 
 def _mesh_args(verts, faces):

@@ -15,6 +15,10 @@ k_icp_* kernels of csrc/mr_points.hip). Neither is differentiable.
 same neighbour search, then a damped Gauss-Newton step on the point-to-plane residual against the target's normals,
 given or estimated with ``estimate_pointcloud_normals``. Not differentiable.
 
+``iterative_closest_point_to_mesh`` is a third: the clouds register onto mesh surfaces (kernels.icp_mesh,
+csrc/mr_icpmesh.hip), the same Gauss-Newton step against the closest surface points and the distance function's
+gradient there. Not differentiable.
+
 ``knn_points`` (K <= 32 nearest neighbours, csrc/mr_knn.hip; ``dists`` is differentiable) and ``knn_gather``.
 
 ``ball_query`` (the first K neighbours inside a radius, any K, csrc/mr_ballquery.hip; ``dists`` is differentiable) and
@@ -36,7 +40,7 @@ import torch
 
 from . import _lib, kernels
 from .kernels import SamplePoints, _require_cuda, face_areas
-from .structures import Pointclouds
+from .structures import Meshes, Pointclouds
 
 _FACES_CACHE: dict = {}
 
@@ -216,6 +220,95 @@ def iterative_closest_point_to_plane(X, Y, Y_normals=None, init_transform=None, 
     converged, iters, rmse, xt, rts, hist = kernels.icp_plane(Xt, Yt, Y_normals, xl, yl, init_transform,
                                                               max_iterations, relative_rmse_thr,
                                                               max_correspondence_distance)
+    if isinstance(X, Pointclouds):
+        xt = X.update_padded(xt)
+    return ICPSolution(converged, rmse, xt, _split_rts(rts), [_split_rts(hist[i]) for i in range(iters)])
+
+
+def iterative_closest_point_to_mesh(X, meshes, init_transform=None, max_iterations: int = 100,
+                                    relative_rmse_thr: float = 1e-6, max_correspondence_distance=None,
+                                    min_triangle_area: float = 0.0, verbose: bool = False):
+    """ICP of the clouds X, an (N,P,3) tensor or a Pointclouds, onto the surfaces of the N ``meshes`` (a Meshes; cloud n
+    registers onto mesh n): a rigid Gauss-Newton estimator on the device-side loop of ``iterative_closest_point`` (a
+    convention of this library; upstream has none). The scan is the moving cloud and the target the surface itself:
+    every point has a counterpart on a complete model and there is no sampling-density floor. Returns
+    ``ICPSolution(converged, rmse (N,), Xt, RTs, t_history)``; ``rmse`` is the point-to-plane rmse below.
+
+    ``meshes`` may be a ``Meshes.extend(N)`` batch, whose one copy of vertices and faces every cloud then reads.
+    ``min_triangle_area`` defaults to 0, the true surface, not upstream's 5e-3 of ``point_mesh_face_distance`` (a loss
+    setting, under which a face below that area counts as its three edges). ``init_transform`` is an (R, T, s) triple
+    whose ``s`` stays fixed. With ``max_correspondence_distance`` d (None, or a float >= 0) a pair is valid iff its
+    float32 squared distance is <= float32(d)^2 rounded once; without, every pair is valid.
+
+    Per cloud n with L1 points, mesh n with T_n faces and (R, T, s) float32, every iteration:
+
+    1. Search. p_i = s (x_i R) + T in float32 for i < L1; f(i) is the face of mesh n with the smallest d(p_i, tri), d
+       exactly ``point_face_distance``'s float32 distance for ``min_triangle_area``. The lowest face index wins a tie;
+       a face with a vertex id out of range is skipped.
+    2. Closest point and normal, in float32 without FMA, from the winner's pair: q_i = (b0 v0 + b1 v1) + b2 v2 per
+       component with the closest point's barycentrics b. n_i is the triangle's unit normal if the plane branch
+       returned the distance; otherwise e = p_i - q_i, l = sqrt((e0 e0 + e1 e1) + e2 e2) and n_i = e / l if l > 1e-8,
+       else 0. That is the gradient of the distance function: where the closest point lies on an edge or vertex
+       shared by several faces, it does not depend on which of the tied faces won. A zero normal contributes nothing
+       and the sign does not matter. A pair is valid iff d <= the squared distance limit; m counts the valid pairs.
+    3. Update. Steps 2 to 6 of ``iterative_closest_point_to_plane``, unchanged, with q_i and n_i in place of y_j and
+       Y_normals_j: float64 A and b about c = s (mx R) + T; lam = 1e-9 trace(A) / 6; the 6x6 Cholesky and Rodrigues;
+       one rounding to float32; rmse = float32(sqrt(sum_valid ((p'_i - q_i).n_i)^2 / max(m, 1))) under the new
+       transform; rel = (prev - rmse) / prev in float32, 1 on the first iteration, and a cloud is done when
+       rel <= ``relative_rmse_thr``. A cloud with m == 0 (an empty cloud, a mesh with no usable face, no pair within
+       the distance) keeps its transform bit for bit, reports rmse 0 and counts as done.
+
+    Four launches an iteration, no (P, T) matrix, the host reads two status words every few iterations (kernels.icp_mesh,
+    csrc/mr_icpmesh.hip); the triangle records are built once per call. Rigid only, a brute-force scan of every face,
+    the mesh fixed during the call, deterministic, not differentiable, no CPU fallback."""
+    who = "iterative_closest_point_to_mesh"
+    if verbose:
+        raise NotImplementedError(f"{who}: verbose=True is not built")
+    if not isinstance(meshes, Meshes):
+        raise ValueError(f"{who}: meshes must be a Meshes")
+    Xt, xc, xl = _clouds_and_lengths(X, who)
+    b, dim = Xt.shape[0], Xt.shape[2]
+    if b != len(meshes):
+        raise ValueError("meshes and pointclouds must be equal sized batches")
+    if b < 1:
+        raise ValueError(f"{who}: the batch is empty")
+    if init_transform is not None:
+        try:
+            R, T, s = init_transform
+            assert tuple(R.shape) == (b, dim, dim) and tuple(T.shape) == (b, dim) and tuple(s.shape) == (b,)
+        except Exception:
+            raise ValueError("The initial transformation init_transform has to be a named tuple SimilarityTransform "
+                             "with elements (R, T, s). R are dim x dim orthonormal matrices of shape "
+                             "(minibatch, dim, dim), T is a batch of dim-dimensional translations of shape "
+                             "(minibatch, dim) and s is a batch of scalars of shape (minibatch,).") from None
+
+    def nonneg(v, name):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            f = float("nan")
+        if isinstance(v, bool) or not f >= 0.0:
+            raise ValueError(f"{who}: {name} must be a float >= 0")
+        return f
+
+    if max_correspondence_distance is not None:
+        max_correspondence_distance = nonneg(max_correspondence_distance, "max_correspondence_distance")
+    min_triangle_area = nonneg(min_triangle_area, "min_triangle_area")
+    if dim != 3:
+        raise NotImplementedError(f"{who}: only D = 3 is built")
+    if meshes.is_shared():  # one copy of the vertices and faces: every cloud's range is the whole table
+        verts = meshes.shared_verts()
+        faces, first, count, max_faces = kernels.mesh_face_table([meshes.shared_faces()], (verts.shape[0],))
+        first, count = first.expand(b).contiguous(), count.expand(b).contiguous()
+    else:
+        verts = meshes.verts_packed()
+        faces, first, count, max_faces = meshes._face_table()
+    _refuse_grad(who, Xt, verts, *(init_transform or ()))
+    _require_cuda(Xt, verts, *(init_transform or ()))
+    batch = kernels.PointMeshBatch(None, xl, Xt.shape[1], faces, first, count, max_faces)
+    converged, iters, rmse, xt, rts, hist = kernels.icp_mesh(Xt, verts, batch, xl, init_transform, max_iterations,
+                                                             relative_rmse_thr, max_correspondence_distance,
+                                                             min_triangle_area)
     if isinstance(X, Pointclouds):
         xt = X.update_padded(xt)
     return ICPSolution(converged, rmse, xt, _split_rts(rts), [_split_rts(hist[i]) for i in range(iters)])
