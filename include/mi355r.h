@@ -851,6 +851,42 @@ int32_t mr_timing_read(int32_t* launches, double* total_ms, int32_t n);
 const char* mr_timing_kernel_name(int32_t k);
 int32_t mr_timing_kernel_count(void);
 
+/* A uniform-grid index over the targets of a neighbour search, and mr_knn_points through it.
+ *
+ * mr_point_grid_build sorts p[n, :lengths[n]] (p (N,P,3); lengths NULL: P) into the cells of one uniform grid per
+ * cloud, in `grid`, a device buffer of mr_point_grid_bytes(N, P) bytes that holds no pointers. Per cloud: the bounding
+ * box lo .. hi of its points; a cell size h > 0 and dims g = (gx, gy, gz) >= 1 chosen on the device, aiming at 4 points
+ * a cell in a uniformly filled box, with gx gy gz <= min(max(lengths[n], 1), P, 2^24) and g_a <= 1024; the cell of a
+ * point along axis a is clamp(int(floor((p_a - lo_a) * (1 / h))), 0, g_a - 1) in float32. An axis of zero extent has
+ * g_a = 1; an empty cloud, coincident points and a cloud with a coordinate that is not finite have one cell (the
+ * search then visits every target of that cloud). Four launches, integer atomics, no memset, nothing read back; the
+ * order of the targets inside a cell may differ from run to run, and no result depends on it. The workspace is only
+ * used during the call. mr_point_grid_describe copies out, per cloud, dims (N,3), origin_cell (N,4) = lo and h, and the
+ * largest number of points in one cell (N) into host arrays (each may be NULL); it synchronises `stream`: for tests
+ * and tools.
+ *
+ * mr_knn_points_grid is mr_knn_points, argument for argument and bit for bit in dists and idx, for a `grid` built
+ * from these p2 and lengths2: one launch, a query per lane, which visits the cells in cube rings r = 0, 1, ... around
+ * the query's own cell (a query outside the box takes the nearest cell) and stops after ring r >= 1 once it holds K
+ * neighbours and the K-th distance is strictly below ((r - 2^-6) h)^2 (1 - 2^-18) (norm 1: (r - 2^-6) h (1 - 2^-18)),
+ * a lower bound on the float32 distance of every target in the cells beyond, or when the rings cover the grid.
+ * `visited` (device, may be NULL) is one counter the caller clears: every workgroup adds the number of (query, target)
+ * distances it evaluated. Nothing read from `grid` is trusted for addressing: a grid of other clouds of the same
+ * shapes gives wrong neighbours with idx in [-1, P2), never a fault. The workspace is not used but must be given.
+ * MR_EINVAL for NULL or non-positive sizes, K < 1 or a norm other than 1 and 2; MR_EUNSUPPORTED for N > 65535, clouds
+ * too large for 32-bit point ids and K > 32; MR_EWORKSPACE ("too small") for the grid buffer and the workspaces; all
+ * before any GPU call. The *_bytes / *_workspace functions return a multiple of 256, or 0 out of range. */
+size_t mr_point_grid_bytes(int64_t N, int64_t P);
+size_t mr_point_grid_build_workspace(int64_t N, int64_t P);
+int32_t mr_point_grid_build(const float* p, int64_t N, int64_t P, const int64_t* lengths, void* grid, size_t grid_bytes,
+                            void* ws, size_t ws_bytes, void* stream);
+size_t mr_knn_points_grid_workspace(int64_t N, int64_t P1, int64_t P2, int32_t K);
+int32_t mr_knn_points_grid(const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2, const int64_t* lengths1,
+                           const int64_t* lengths2, const void* grid, size_t grid_bytes, int32_t norm, int32_t K,
+                           float* dists, int32_t* idx, uint64_t* visited, void* ws, size_t ws_bytes, void* stream);
+int32_t mr_point_grid_describe(const void* grid, int64_t N, int64_t P, int32_t* dims, float* origin_cell,
+                               int32_t* max_cell_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,7 @@
 // the workgroup's tile of queries and range of targets (scan_tile); for the K-deep lists, the insertion into the
 // register-resident ascending key list, the scan of a target range into the lists, the store of a partial list and
 // the merge of a query's partial lists. (k_frames keeps its own tile prologue and key store: mr_normals.hip says why.)
+// mr_grid.hip's k_knn_grid takes the insertion, the decoding store (knn_store) and the argument check (check_knn).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,6 +15,7 @@
 #define MRK_WANT_GROUPS 1024   // workgroups a split launch aims for
 #define MRK_SPLIT_ALIGN 64     // a split's targets are a multiple of this
 #define MRK_TBLOCK 256         // threads of the per-query kernels
+#define MRK_MAXK 32            // the deepest list mr_knn_points and mr_knn_points_grid keep
 
 namespace {
 
@@ -67,6 +69,17 @@ inline size_t knn_ws_bytes(int64_t N, int64_t P1, int K, const KnnGeom& g) {
   Carver c(nullptr);
   c.take<u64>((g.splits > 1 ? (size_t)(N * P1) * (size_t)K * (size_t)g.splits : 0) + 1);
   return c.off;
+}
+
+// What mr_knn_points, its backward and mr_knn_points_grid check first.
+inline int check_knn(const char* who, const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2, int32_t norm,
+                     int32_t K) {
+  if (int rc = check_sizes(who, N, P1, P2)) return rc;
+  if (K < 1) return set_err(MR_EINVAL, "%s: K must be >= 1", who);
+  if (K > MRK_MAXK) return set_err(MR_EUNSUPPORTED, "%s: K > %d is not built", who, MRK_MAXK);
+  if (norm != 1 && norm != 2) return set_err(MR_EINVAL, "%s: norm must be 1 or 2", who);
+  if (!p1 || !p2) return set_err(MR_EINVAL, "%s: p1 / p2 is NULL", who);
+  return MR_OK;
 }
 
 // A scanning workgroup's share of grid (query tiles * splits, N): cloud n, queries from q0 of its lq, and targets
@@ -131,6 +144,20 @@ __device__ __forceinline__ void knn_store_keys(const u64 (&L)[KB], bool row_ok, 
 #pragma unroll
   for (int j = 0; j < KB; ++j) {
     if (j < K) o[j] = row_ok ? L[j] : ~0ull;
+  }
+}
+
+// The first K slots of a list as dists / idx: 0 / -1 for a slot that was never filled (or a row past its length).
+template <int KB>
+__device__ __forceinline__ void knn_store(const u64 (&L)[KB], bool row_ok, int K, float* __restrict__ od,
+                                          int32_t* __restrict__ oi) {
+#pragma unroll
+  for (int s = 0; s < KB; ++s) {
+    const bool ok = row_ok && L[s] != ~0ull;
+    if (s < K) {
+      od[s] = ok ? key_dist(L[s]) : 0.0f;
+      oi[s] = ok ? (int32_t)key_index(L[s]) : -1;
+    }
   }
 }
 

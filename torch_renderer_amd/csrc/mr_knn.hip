@@ -20,9 +20,10 @@
 //   k_knn_bwd     one thread per query: grad_p1 = sum_k 2 g (p1 - p2[idx]) (norm 1: g sign(.)) with a plain store, and
 //                 the same addends into the targets' rows with 64-bit fixed-point integer atomics (mr_common.h);
 //   k_knn_bwd_p2  grad_p2 = -(row). Slots with idx < 0 contribute nothing and their g is not read.
-// The geometry (knn_geom), the split constants and the list code are mr_knn.h's, shared with mr_normals.hip and
-// mr_ballquery.hip. The two bucket ladders below stay macros of this file: mr_normals.hip's run over other buckets
-// (8 .. 64) with other arguments, and one dispatcher for both would need the kernel as a template template argument.
+// The geometry (knn_geom), the split constants, the list code with its decoding store (knn_store) and the argument
+// check (check_knn) are mr_knn.h's, shared with mr_normals.hip, mr_ballquery.hip and mr_grid.hip. The two bucket
+// ladders below stay macros of this file: mr_normals.hip's run over other buckets (8 .. 64) with other arguments, and
+// one dispatcher for both would need the kernel as a template template argument.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -32,23 +33,7 @@
 #include "mr_cloud.h"
 #include "mr_knn.h"
 
-#define MRK_MAXK 32
-
 namespace {
-
-// The first K slots of a list as dists / idx: 0 / -1 for a slot that was never filled (or a row past its length).
-template <int KB>
-__device__ __forceinline__ void knn_store(const u64 (&L)[KB], bool row_ok, int K, float* __restrict__ od,
-                                          int32_t* __restrict__ oi) {
-#pragma unroll
-  for (int s = 0; s < KB; ++s) {
-    const bool ok = row_ok && L[s] != ~0ull;
-    if (s < K) {
-      od[s] = ok ? key_dist(L[s]) : 0.0f;
-      oi[s] = ok ? (int32_t)key_index(L[s]) : -1;
-    }
-  }
-}
 
 // grid (query tiles * splits, N). part != NULL: (N, P1, splits, K) keys; else dists / idx (N, P1, K).
 template <int NORM, int KB, int Q>
@@ -136,16 +121,6 @@ __global__ void __launch_bounds__(MRK_TBLOCK) k_knn_bwd_p2(const u64* __restrict
 __global__ void __launch_bounds__(MRK_TBLOCK) k_zero_words(u64* __restrict__ p, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * MRK_TBLOCK + threadIdx.x;
   if (i < n) p[i] = 0ull;
-}
-
-int check_knn(const char* who, const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2, int32_t norm,
-              int32_t K) {
-  if (int rc = check_sizes(who, N, P1, P2)) return rc;
-  if (K < 1) return set_err(MR_EINVAL, "%s: K must be >= 1", who);
-  if (K > MRK_MAXK) return set_err(MR_EUNSUPPORTED, "%s: K > %d is not built", who, MRK_MAXK);
-  if (norm != 1 && norm != 2) return set_err(MR_EINVAL, "%s: norm must be 1 or 2", who);
-  if (!p1 || !p2) return set_err(MR_EINVAL, "%s: p1 / p2 is NULL", who);
-  return MR_OK;
 }
 
 // The gradient of a neighbour search's dists behind mr_knn_points_backward and mr_ball_query_backward, whose own

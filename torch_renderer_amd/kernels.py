@@ -331,27 +331,28 @@ def _neighbour_forward(workspace, launch, scalar, p1f, p2f, l1, l2, N, P1, P2, K
 
 
 class _NeighbourDists(torch.autograd.Function):
-    """What KnnPoints and BallQuery are: a search ``_search(p1, p2, lengths1, lengths2, K, x)`` -> (dists, idx, the
+    """What KnnPoints, KnnPointsGrid and BallQuery are: a search ``_search(p1, p2, lengths1, lengths2, K, x, *more)``
+    (``more``: further arguments without a gradient, KnnPointsGrid's grid buffer) -> (dists, idx, the
     float32 clouds and int64 lengths it ran on, the checked K) with the gradient of ``dists`` w.r.t. p1 and p2 (``idx``
     is not differentiable): three launches backward and no memset, the many-to-one p2 side summed in fixed point, by
     the ``_backward`` entry point, which takes ``x`` as its norm if ``_pass_norm``."""
 
     @staticmethod
-    def forward(ctx, p1, p2, lengths1, lengths2, K, x):
+    def forward(ctx, p1, p2, lengths1, lengths2, K, x, *more):
         cls = ctx._forward_cls  # the subclass that was applied
-        dists, idx, (p1f, p2f, l1, l2), K = cls._search(p1, p2, lengths1, lengths2, K, x)
+        dists, idx, (p1f, p2f, l1, l2), K = cls._search(p1, p2, lengths1, lengths2, K, x, *more)
         ctx.mark_non_differentiable(idx)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(p1f, p2f, idx, l1, l2)
-        ctx.args = (K, (int(x),) if cls._pass_norm else (), p1.dtype, p2.dtype)
+        ctx.args = (K, (int(x),) if cls._pass_norm else (), p1.dtype, p2.dtype, len(more))
         return dists, idx
 
     @staticmethod
     def backward(ctx, g, _g_idx):
         if g is None:
-            return (None,) * 6
+            return (None,) * (6 + ctx.args[4])
         p1f, p2f, idx, l1, l2 = ctx.saved_tensors
-        K, norm, dt1, dt2 = ctx.args
+        K, norm, dt1, dt2, more = ctx.args
         g = g.detach().float().contiguous()
         _require_cuda(g)
         L = _lib.load()
@@ -361,7 +362,7 @@ class _NeighbourDists(torch.autograd.Function):
         ws, wsb = _workspace(getattr(L, name + "_workspace"), p1f.device, N, P1, P2, K)
         check(getattr(L, name)(ptr(p1f), ptr(p2f), N, P1, P2, ptr(l1), ptr(l2), *norm, K, ptr(idx), ptr(g), ptr(g1),
                                ptr(g2), ptr(ws), wsb, _lib.stream_handle(p1f.device)))
-        return g1.to(dt1), g2.to(dt2), None, None, None, None
+        return (g1.to(dt1), g2.to(dt2), None, None, None, None) + (None,) * more
 
 
 # --------------------------------------------------------------------------- K nearest neighbours (csrc/mr_knn.hip)
@@ -403,6 +404,82 @@ class KnnPoints(_NeighbourDists):
     """knn_points with the gradient of ``dists`` w.r.t. p1 and p2 (``idx`` is not differentiable): three launches
     backward and no memset, the many-to-one p2 side summed in fixed point (mr_knn_points_backward)."""
     _search, _backward, _pass_norm = staticmethod(_knn_search), "mr_knn_points_backward", True
+
+
+# --------------------------------------------------------------------------- point grid (csrc/mr_grid.hip)
+def _grid_points(points, lengths):
+    """The checked inputs of a grid build: (float32 points, int64 lengths or None, N, P)."""
+    if points.dim() != 3:
+        raise ValueError("point grid: points must be an (N, P, 3) tensor")
+    if points.shape[2] != 3:
+        raise NotImplementedError("point grid: only D = 3 is built")
+    N, P = points.shape[0], points.shape[1]
+    if N < 1 or P < 1:
+        raise ValueError("point grid: N and P must be >= 1")
+    if lengths is not None:
+        if tuple(lengths.shape) != (N,):
+            raise ValueError("lengths must be of shape (N,)")
+        lengths = lengths.detach().to(torch.int64).contiguous()
+    _require_cuda(points, lengths)
+    return points.detach().float().contiguous(), lengths, N, P
+
+
+def point_grid_build(points, lengths=None):
+    """The grid buffer (uint8, mr_point_grid_bytes) of points[n, :lengths[n]] (N,P,3): every cloud's points sorted into
+    the cells of a uniform grid whose cell size and dims are chosen on the device. Four launches, nothing read back
+    (mr_point_grid_build)."""
+    pf, l, N, P = _grid_points(points, lengths)
+    L = _lib.load()
+    grid, gb = _workspace(L.mr_point_grid_bytes, pf.device, N, P, what="point grid: the clouds are too large")
+    ws, wsb = _workspace(L.mr_point_grid_build_workspace, pf.device, N, P)
+    check(L.mr_point_grid_build(ptr(pf), N, P, ptr(l), ptr(grid), gb, ptr(ws), wsb, _lib.stream_handle(pf.device)))
+    return grid
+
+
+def point_grid_describe(grid, N, P):
+    """(dims (N,3) int32, origin_cell (N,4) float32 = lo xyz and the cell size, max_cell_count (N,) int32) of a grid
+    buffer of point_grid_build, on the host. Synchronises: for tests and tools (mr_point_grid_describe)."""
+    _require_cuda(grid)
+    N, P = int(N), int(P)
+    L = _lib.load()
+    if grid.dtype != torch.uint8 or grid.numel() < _ws_size(L.mr_point_grid_bytes, N, P) or not grid.is_contiguous():
+        raise ValueError("point grid: not a grid buffer of these shapes")
+    dims, cell, most = torch.empty((N, 3), dtype=torch.int32), torch.empty((N, 4)), torch.empty(N, dtype=torch.int32)
+    check(L.mr_point_grid_describe(ptr(grid), N, P, ptr(dims), ptr(cell), ptr(most), _lib.stream_handle(grid.device)))
+    return dims, cell, most
+
+
+def _knn_grid_search(p1, p2, lengths1, lengths2, K, norm, grid, visited=None):
+    K = _knn_k(K)
+    p1f, p2f, l1, l2, N, P1, P2 = _cloud_args(p1, p2, lengths1, lengths2, norm)
+    _require_cuda(grid, visited)
+    L = _lib.load()
+    gb = _ws_size(L.mr_point_grid_bytes, N, P2)
+    if grid.dtype != torch.uint8 or grid.numel() != gb or gb == 0 or not grid.is_contiguous():
+        raise ValueError("knn_points: the grid buffer was not built for a target batch of this shape")
+    if visited is not None and (visited.dtype != torch.int64 or visited.numel() != 1):
+        raise ValueError("knn_points: visited must be one int64")
+    dev = p1f.device
+    dists = torch.empty((N, P1, K), device=dev)
+    idx = torch.empty((N, P1, K), dtype=torch.int32, device=dev)
+    ws, wsb = _workspace(L.mr_knn_points_grid_workspace, dev, N, P1, P2, K)
+    check(L.mr_knn_points_grid(ptr(p1f), ptr(p2f), N, P1, P2, ptr(l1), ptr(l2), ptr(grid), gb, int(norm), K,
+                               ptr(dists), ptr(idx), ptr(visited), ptr(ws), wsb, _lib.stream_handle(dev)))
+    return dists, idx, (p1f, p2f, l1, l2), K
+
+
+def knn_points_grid(p1, p2, grid, lengths1=None, lengths2=None, K=1, norm=2, visited=None):
+    """knn_points' (dists, idx), bit for bit, through ``grid`` = point_grid_build(p2, lengths2): a query visits the
+    cells around its own in growing cube rings and stops once no unvisited cell can hold a nearer point. ``visited``
+    (one int64 on the device, cleared by the caller) gains the number of distances evaluated. A grid of other clouds
+    of the same shape gives wrong neighbours, idx still in [-1, P2). No autograd; one launch (mr_knn_points_grid)."""
+    return _knn_grid_search(p1, p2, lengths1, lengths2, K, norm, grid, visited)[:2]
+
+
+class KnnPointsGrid(_NeighbourDists):
+    """KnnPoints with the forward search through a grid buffer, ``apply(p1, p2, lengths1, lengths2, K, norm, grid)``:
+    the same idx, so the same backward (mr_knn_points_backward)."""
+    _search, _backward, _pass_norm = staticmethod(_knn_grid_search), "mr_knn_points_backward", True
 
 
 # --------------------------------------------------------------------------- radius neighbourhoods (csrc/mr_ballquery.hip)

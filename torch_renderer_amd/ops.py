@@ -20,6 +20,8 @@ csrc/mr_icpmesh.hip), the same Gauss-Newton step against the closest surface poi
 gradient there. Not differentiable.
 
 ``knn_points`` (K <= 32 nearest neighbours, csrc/mr_knn.hip; ``dists`` is differentiable) and ``knn_gather``.
+``PointGrid`` (csrc/mr_grid.hip) is a uniform-grid index over the targets that ``knn_points(..., grid=)`` searches
+instead of scanning every target, with the same result bit for bit.
 
 ``ball_query`` (the first K neighbours inside a radius, any K, csrc/mr_ballquery.hip; ``dists`` is differentiable) and
 ``masked_gather``.
@@ -406,14 +408,69 @@ def knn_gather(x, idx, lengths=None):
     return out.masked_fill(pad[:, None, :, None].expand(-1, L, -1, U), 0.0)
 
 
+class PointGrid:
+    """A uniform-grid index over the clouds ``points`` (an (N,P,3) tensor with optional ``lengths`` (N,), or a
+    ``Pointclouds``, which brings its own lengths), for ``knn_points(p1, points, lengths2=lengths, grid=...)``. Built on
+    the device in four launches (kernels.point_grid_build, csrc/mr_grid.hip); with a tensor nothing synchronises, and
+    build plus search capture into a HIP graph. It holds no gradient and keeps a copy of the coordinates, so it
+    remembers what it was built from — the tensor's identity, ``_version`` and shape, and the lengths — and
+    ``knn_points`` refuses it for anything else: rebuild it whenever the points change. One grid per cloud, single
+    level: a far outlier stretches the box and the search degrades towards the brute-force scan (still correct)."""
+
+    def __init__(self, points, lengths=None):
+        self._remember(points, lengths)
+        self.buffer = kernels.point_grid_build(self._ref(), self.lengths)
+
+    def _remember(self, points, lengths):
+        """What the grid is built from (host only): the padded tensor, by weak reference, with its version and shape;
+        the lengths tensor; whether every cloud is known on the host to be full (a call without lengths2 then fits)."""
+        self.full = lengths is None
+        if isinstance(points, Pointclouds):
+            if lengths is not None:
+                raise ValueError("PointGrid: a Pointclouds brings its own lengths")
+            cloud, points = points, points.points_padded()
+            self.full = all(c == points.shape[1] for c in cloud.counts())
+            lengths = cloud.num_points_per_cloud()
+        if not torch.is_tensor(points) or points.dim() != 3:
+            raise ValueError("PointGrid: points must be an (N, P, 3) tensor or a Pointclouds")
+        if lengths is not None and (not torch.is_tensor(lengths) or tuple(lengths.shape) != (points.shape[0],)):
+            raise ValueError("lengths must be of shape (N,)")
+        self._ref, self._version, self.shape = weakref.ref(points), points._version, tuple(points.shape)
+        self.lengths = lengths
+        self._lengths_version = None if lengths is None else lengths._version
+
+    def _check(self, p2, lengths2):
+        """ValueError unless the grid was built from this p2 (not modified since) with these lengths2."""
+        if self._ref() is not p2 or p2._version != self._version or tuple(p2.shape) != self.shape:
+            raise ValueError("knn_points: the grid was not built from this p2 (another tensor, or modified in place "
+                             "since); rebuild it with PointGrid(p2, lengths2)")
+        if lengths2 is None:
+            same = self.lengths is None or self.full
+        else:
+            same = lengths2 is self.lengths and lengths2._version == self._lengths_version
+        if not same:
+            raise ValueError("knn_points: the grid was not built with these lengths2; rebuild it with "
+                             "PointGrid(p2, lengths2)")
+
+    def describe(self):
+        """(dims (N,3) int32, origin_cell (N,4) = lo xyz and the cell size, max_cell_count (N,) int32) on the host.
+        Synchronises: for tests and tools."""
+        return kernels.point_grid_describe(self.buffer, self.shape[0], self.shape[1])
+
+
 def knn_points(p1, p2, lengths1=None, lengths2=None, norm: int = 2, K: int = 1, version: int = -1,
-               return_nn: bool = False, return_sorted: bool = True):
+               return_nn: bool = False, return_sorted: bool = True, grid: Optional[PointGrid] = None):
     """``pytorch3d.ops.knn_points``: for every point of p1 (N,P1,3) its K <= 32 nearest points of p2 (N,P2,3), as a
     namedtuple (dists (N,P1,K), idx (N,P1,K) int64, knn (N,P1,K,3) or None). dists is the squared L2 (norm 2) or L1
     (norm 1) distance in float32, ascending; equal distances take the lower index. Entries past min(K, lengths2[n])
     and rows past lengths1[n] are padded with 0 in both. The output is always sorted (a valid answer for
     ``return_sorted=False``); ``version`` is accepted and ignored. dists is differentiable w.r.t. p1 and p2
-    (kernels.KnnPoints, csrc/mr_knn.hip), knn through the gather."""
+    (kernels.KnnPoints, csrc/mr_knn.hip), knn through the gather.
+
+    ``grid=PointGrid(p2, lengths2)`` runs the search through that index instead of the brute-force scan
+    (kernels.KnnPointsGrid, csrc/mr_grid.hip): the same dists, idx and knn bit for bit and the same backward. A grid
+    that was not built from this p2 (the same tensor, not modified in place since) with these lengths2 raises
+    ValueError. Without it the call is the brute-force kernel; nothing routes automatically."""
     if p1.dim() != 3 or p2.dim() != 3:
         raise ValueError("pts1 and pts2 must be (N, P, D) tensors.")
     if p1.shape[0] != p2.shape[0]:
@@ -425,7 +482,13 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, norm: int = 2, K: int = 1, 
     for l in (lengths1, lengths2):
         if l is not None and tuple(l.shape) != (p1.shape[0],):
             raise ValueError("lengths must be of shape (N,)")
-    dists, idx = kernels.KnnPoints.apply(p1, p2, lengths1, lengths2, K, norm)
+    if grid is None:
+        dists, idx = kernels.KnnPoints.apply(p1, p2, lengths1, lengths2, K, norm)
+    else:
+        if not isinstance(grid, PointGrid):
+            raise ValueError("knn_points: grid must be a PointGrid or None")
+        grid._check(p2, lengths2)
+        dists, idx = kernels.KnnPointsGrid.apply(p1, p2, lengths1, lengths2, K, norm, grid.buffer)
     dists = dists.to(p1.dtype)
     idx = idx.clamp(min=0).long()
     return _KNN(dists=dists, idx=idx, knn=knn_gather(p2, idx, lengths2) if return_nn else None)
