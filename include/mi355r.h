@@ -887,6 +887,34 @@ int32_t mr_knn_points_grid(const float* p1, const float* p2, int64_t N, int64_t 
 int32_t mr_point_grid_describe(const void* grid, int64_t N, int64_t P, int32_t* dims, float* origin_cell,
                                int32_t* max_cell_count, void* stream);
 
+/* The ICP loops through a point grid of the targets: mr_icp_iterate_grid is mr_icp_iterate, and
+ * mr_icp_plane_iterate_grid is mr_icp_plane_iterate, argument for argument and bit for bit in rts, history, rmse and
+ * status, with `grid` (a buffer of mr_point_grid_build for these y and y_lengths, grid_bytes >= mr_point_grid_bytes(N,
+ * P2)) and `visited` added. The rule is the search of mr_icp_iterate, through the grid, with the same key in `ws`:
+ * the first launch of an iteration leaves, per source point, the key of the nearest target that the brute-force scan
+ * leaves (the float32 squared distance and the lowest index on ties; for a point whose every distance is +inf or a
+ * NaN, distance +inf and index 0); the three other launches, the workspaces (mr_icp_workspace,
+ * mr_icp_plane_workspace), mr_icp_init and mr_icp_transform are used as they are, and a registration may change
+ * between the two entry points from one call to the next. One source point per lane walks the cells in cube rings as
+ * mr_knn_points_grid does with K = 1. With max_dist2 < +inf the plane estimator's walk also stops after ring r >= 1
+ * once ((r - 2^-6) h)^2 (1 - 2^-18) > max_dist2: no target beyond the rings can form a valid pair, and a source point
+ * without a valid pair contributes nothing whichever target its key names. `visited` (device, may be NULL) is one
+ * counter the caller clears: every workgroup of an iteration that is not idle adds the number of (source, target)
+ * distances it evaluated. Nothing read from `grid` is trusted for addressing: a grid of other clouds of the same
+ * shapes gives wrong correspondences inside the target, never a fault. MR_EINVAL for a NULL grid and for what the
+ * siblings refuse (sizes, flags, max_dist2, max_iterations, iterations, NULL pointers); MR_EUNSUPPORTED as the
+ * siblings; MR_EWORKSPACE ("too small") for the grid buffer and the workspace; all before any GPU call. */
+int32_t mr_icp_iterate_grid(const float* x, const float* y, int64_t N, int64_t P1, int64_t P2, const int64_t* x_lengths,
+                            const int64_t* y_lengths, const void* grid, size_t grid_bytes, int32_t flags,
+                            float relative_rmse_thr, int32_t max_iterations, int32_t iterations, float* rts,
+                            float* history, float* rmse, int32_t* status, uint64_t* visited, void* ws, size_t ws_bytes,
+                            void* stream);
+int32_t mr_icp_plane_iterate_grid(const float* x, const float* y, const float* y_normals, int64_t N, int64_t P1,
+                                  int64_t P2, const int64_t* x_lengths, const int64_t* y_lengths, const void* grid,
+                                  size_t grid_bytes, float max_dist2, float relative_rmse_thr, int32_t max_iterations,
+                                  int32_t iterations, float* rts, float* history, float* rmse, int32_t* status,
+                                  uint64_t* visited, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -184,6 +184,10 @@ _SIGS = [
     ("mr_knn_points_grid", _I32, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _SZ, _I32, _I32, _VP, _VP, _VP, _VP, _SZ,
                                   _VP]),
     ("mr_point_grid_describe", _I32, [_VP, _I64, _I64, _VP, _VP, _VP, _VP]),
+    ("mr_icp_iterate_grid", _I32, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _SZ, _I32, ctypes.c_float, _I32, _I32, _VP,
+                                   _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    ("mr_icp_plane_iterate_grid", _I32, [_VP, _VP, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _SZ, ctypes.c_float,
+                                         ctypes.c_float, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     ("mr_ball_query_geometry", _I32, [_I64, _I64, _I64, _I32, c_i32_p, c_i32_p, c_i32_p]),
     ("mr_ball_query_workspace", _SZ, [_I64, _I64, _I64, _I32]),
     ("mr_ball_query", _I32, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, ctypes.c_float, _I32, _VP, _VP, _VP, _SZ, _VP]),

@@ -26,6 +26,8 @@
 //                   Procrustes problem by a fixed-sweep Jacobi SVD in float64, then sums its tile of the residual
 //                   under the new transform) and k_icp_status (rmse, relative drop, the device status words every
 //                   kernel of a later iteration reads first). No float atomics, every sum in a fixed order.
+//                   mr_icp_iterate_grid / mr_icp_plane_iterate_grid put k_icp_nn_grid in k_icp_nn's place: the same
+//                   key per source point from a walk through a point grid of the targets (mr_grid.h's grid_walk).
 //   k_icp_plane_*   the point-to-plane estimator on the same loop (mr_icp_plane_iterate): k_icp_nn as it is, then
 //                   k_icp_plane_moments (validity, float64 sums of J J^T, J r and the pair count per tile),
 //                   k_icp_plane_solve (a damped 6x6 Cholesky step about the transformed source mean, then the new
@@ -40,6 +42,7 @@
 #include "mr_common.h"
 #include "mr_host.h"
 #include "mr_cloud.h"
+#include "mr_grid.h"
 #include "mr_icp.h"
 
 #define MRN_Q 4                        // queries per thread
@@ -460,6 +463,55 @@ __global__ void __launch_bounds__(MRN_BLOCK) k_icp_nn(const float* __restrict__ 
   const int64_t Pq = g.P[0], Pt = g.P[1];
   nn_chunk_search<2>(sm, x + 3 * n * Pq, y + 3 * n * Pt, cloud_len(xl, n, Pq), cloud_len(yl, n, Pt), blockIdx.x,
                      g.nchunk[0], g.chunk[0], rts + n * MRI_RTS, true, key_x + n * Pq);
+}
+
+// k_icp_nn through a point grid of the targets (mr_grid.hip builds it): grid (blocks over P1, N), one wave a workgroup,
+// a source point per lane as in k_knn_grid; the lane transforms its point, walks the rings with a one-entry list and
+// stores its key with a plain store (it owns the query). A cloud without targets stores nothing: the key stays
+// all-ones, "no target" to the moments kernels.
+//
+// The key is k_icp_nn's, bit for bit. nn_chunk_search starts every chunk at (+inf, the chunk's first index) and lets a
+// target in on a strictly smaller distance, and the chunks merge by atomicMin: the result is the smallest 64-bit key
+// among nn_key(+inf, 0) and the keys of the targets whose distance is below +inf. So the list starts at
+// nn_key(+inf, 0), not at k_knn_grid's all-ones, and a candidate enters on a strictly smaller 64-bit key
+// (visit_range): a distance of +inf gives a key >= the start value, a nan's bits lie above +inf's, and neither
+// displaces it; a query whose every distance is +inf or a nan ends with nn_key(+inf, 0) on both routes. Such a lane
+// never stops early (inf < ring_bound is false), so it has seen every target when the rings cover the grid.
+//
+// CAP (the plane estimator with max_dist2 < +inf): the lane also stops after ring r >= 1 once ring_bound(r) >
+// max_dist2. Every target beyond the rings then has a float32 distance >= the bound > max_dist2 and could not form a
+// valid pair. If the lane's best is <= max_dist2 it lies strictly below every unvisited distance and is the nearest
+// target; if it is above, so is the nearest target's, and k_icp_plane_moments writes idx = -1 for either key. Nothing
+// downstream reads more of the key than that (DESIGN.md §3 "ICP through a point grid").
+template <bool CAP>
+__global__ void __launch_bounds__(MRG_QBLOCK) k_icp_nn_grid(const float* __restrict__ x, int64_t P1, int64_t P2,
+                                                            const int64_t* __restrict__ xl,
+                                                            const int64_t* __restrict__ yl, int64_t budget,
+                                                            const GridHead* __restrict__ heads,
+                                                            const uint32_t* __restrict__ cell_start,
+                                                            const float4* __restrict__ pts,
+                                                            const float* __restrict__ rts, float max_dist2,
+                                                            const int32_t* __restrict__ status, int max_iter,
+                                                            u64* __restrict__ key_x, u64* __restrict__ visited) {
+  if (icp_idle(status, max_iter)) return;
+  const int64_t n = blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * MRG_QBLOCK + threadIdx.x;
+  const int64_t lq = cloud_len(xl, n, P1);
+  const uint32_t lt = (uint32_t)cloud_len(yl, n, P2);
+  const GridHead H = heads[n];
+  int gx, gy, gz;
+  head_dims(H, budget, gx, gy, gz);
+  uint32_t seen = 0u;
+  if (i < lq && lt > 0u) {
+    const float* __restrict__ q = x + 3 * (n * P1 + i);
+    float qx, qy, qz;
+    sim_apply(rts + n * MRI_RTS, q[0], q[1], q[2], qx, qy, qz);
+    u64 L[1] = {nn_key(__builtin_inff(), 0u)};
+    grid_walk<2, 1, CAP>(H, gx, gy, gz, cell_start + n * (budget + 1), pts + n * P2, lt, (uint32_t)(P2 - 1), qx, qy, qz,
+                         1, max_dist2, L, seen);
+    key_x[n * P1 + i] = L[0];
+  }
+  if (visited) grid_count_visited(seen, visited);
 }
 
 // grid (nblk, N): the moments of a tile of source points against their correspondences. key != NULL: the
@@ -951,6 +1003,136 @@ __global__ void __launch_bounds__(MRR_BLOCK) k_posed_final(const double* __restr
   o[12] = (float)(kf * m[12]);
 }
 
+// ---------------------------------------------------------------------------
+// Host side of the ICP loops: the argument checks and the iterations, which take their search as a launch.
+// ---------------------------------------------------------------------------
+int check_icp(const char* who, const float* x, int64_t N, int64_t P1, int64_t P2) {
+  if (int rc = check_sizes(who, N, P1, P2)) return rc;
+  if (!x) return set_err(MR_EINVAL, "%s: x is NULL", who);
+  return MR_OK;
+}
+
+// What mr_icp_iterate and mr_icp_iterate_grid check first.
+int check_icp_iterate(const char* who, const float* x, const float* y, int64_t N, int64_t P1, int64_t P2,
+                      int32_t flags, int32_t max_iterations, int32_t iterations, const float* rts,
+                      const float* history, const float* rmse, const int32_t* status, const void* ws) {
+  if (int rc = check_icp(who, x, N, P1, P2)) return rc;
+  if (flags & ~MR_ICP_ALL) return set_err(MR_EINVAL, "%s: unknown bits in flags", who);
+  if (max_iterations < 1 || iterations < 0 || (int64_t)max_iterations * N > (1ll << 40) / MRI_RTS)
+    return set_err(MR_EINVAL, "%s: max_iterations must be >= 1 (and the history addressable), iterations >= 0", who);
+  if (!y || !rts || !history || !rmse || !status || !ws) return set_err(MR_EINVAL, "%s: NULL pointer", who);
+  return MR_OK;
+}
+
+// The grid argument of the *_iterate_grid entry points, mr_knn_points_grid's contract: after the sizes are known good.
+int check_icp_grid(const char* who, const void* grid, size_t grid_bytes, int64_t N, int64_t P2, GridBuf& b) {
+  if (!grid) return set_err(MR_EINVAL, "%s: grid is NULL", who);
+  b = carve_grid(grid, N, P2);
+  if (grid_bytes < b.bytes) return set_err(MR_EWORKSPACE, "%s: grid buffer too small", who);
+  return MR_OK;
+}
+
+// The launch of k_icp_nn_grid for a batch, as the search of an iteration.
+struct GridSearch {
+  const float* x;
+  int64_t N, P1, P2;
+  const int64_t *xl, *yl;
+  GridBuf b;
+  const float* rts;
+  float max_dist2;  // +inf: no cap
+  const int32_t* status;
+  int max_iter;
+  u64 *key, *visited;
+  hipStream_t st;
+  int operator()() const {
+    const dim3 g((unsigned)ceil_div(P1, MRG_QBLOCK), (unsigned)N);
+    return launch(KID_NONE, "k_icp_nn_grid", max_dist2 < __builtin_inff() ? k_icp_nn_grid<true> : k_icp_nn_grid<false>, g,
+                  MRG_QBLOCK, 0, st, x, P1, P2, xl, yl, grid_budget(P2), (const GridHead*)b.head,
+                  (const uint32_t*)b.cell_start, (const float4*)b.pts, rts, max_dist2, status, max_iter, key, visited);
+  }
+};
+
+// The launch of k_icp_nn for a batch, as the search of an iteration.
+struct ScanSearch {
+  const float *x, *y;
+  NNGeom g;
+  const int64_t *xl, *yl;
+  const float* rts;
+  const int32_t* status;
+  int max_iter;
+  u64* key;
+  hipStream_t st;
+  int operator()() const {
+    return launch(KID_NONE, "k_icp_nn", k_icp_nn, dim3((unsigned)g.groups[0], (unsigned)g.N), MRN_BLOCK, 0, st, x, y, g,
+                  xl, yl, rts, status, max_iter, key);
+  }
+};
+
+// `iterations` iterations of the point-to-point loop: `search` leaves every source point's key in w.key, the moments,
+// solve and status launches follow.
+template <class Search>
+int icp_iterations(const Search& search, const float* x, const float* y, int64_t N, int64_t P1, int64_t P2,
+                   const int64_t* x_lengths, const int64_t* y_lengths, int32_t flags, float relative_rmse_thr,
+                   int32_t max_iterations, int32_t iterations, float* rts, float* history, float* rmse,
+                   int32_t* status, const IcpWS& w, hipStream_t st) {
+  const dim3 gt((unsigned)w.nblk, (unsigned)N);
+  for (int it = 0; it < iterations; ++it) {
+    if (int rc = search()) return rc;
+    if (int rc = launch(KID_NONE, "k_icp_moments", k_icp_moments, gt, MRR_BLOCK, 0, st, x, y, P1, P2, x_lengths, y_lengths,
+                        (const float*)nullptr, (const double*)w.xc, (const int32_t*)status, max_iterations, w.key, w.idx,
+                        w.mom, w.nblk))
+      return rc;
+    if (int rc = launch(KID_NONE, "k_icp_solve", k_icp_solve, gt, MRR_BLOCK, 0, st, x, y, N, P1, P2, x_lengths,
+                        (const float*)nullptr, (const double*)w.xc, (const double*)w.mom, w.nblk, (const int32_t*)w.idx,
+                        flags, 1e-9, (const int32_t*)status, max_iterations, rts, history, w.res))
+      return rc;
+    if (int rc = launch(KID_NONE, "k_icp_status", k_icp_status, 1, MRR_BLOCK, 0, st, (const double*)w.res, w.nblk, N,
+                        (const double*)w.xc, 1e-9, relative_rmse_thr, max_iterations, rmse, status))
+      return rc;
+  }
+  return MR_OK;
+}
+
+// What mr_icp_plane_iterate and mr_icp_plane_iterate_grid check first.
+int check_icp_plane_iterate(const char* who, const float* x, const float* y, const float* y_normals, int64_t N,
+                            int64_t P1, int64_t P2, float max_dist2, int32_t max_iterations, int32_t iterations,
+                            const float* rts, const float* history, const float* rmse, const int32_t* status,
+                            const void* ws) {
+  if (int rc = check_icp(who, x, N, P1, P2)) return rc;
+  if (!(max_dist2 > 0.0f)) return set_err(MR_EINVAL, "%s: max_dist2 must be > 0 (+inf: no limit)", who);
+  if (max_iterations < 1 || iterations < 0 || (int64_t)max_iterations * N > (1ll << 40) / MRI_RTS)
+    return set_err(MR_EINVAL, "%s: max_iterations must be >= 1 (and the history addressable), iterations >= 0", who);
+  if (!y || !y_normals || !rts || !history || !rmse || !status || !ws) return set_err(MR_EINVAL, "%s: NULL pointer", who);
+  return MR_OK;
+}
+
+// `iterations` iterations of the point-to-plane loop: `search` leaves every source point's key in w.icp.key, the
+// moments, solve and status launches follow.
+template <class Search>
+int icp_plane_iterations(const Search& search, const float* x, const float* y, const float* y_normals, int64_t N,
+                         int64_t P1, int64_t P2, const int64_t* x_lengths, const int64_t* y_lengths,
+                         float max_dist2, float relative_rmse_thr, int32_t max_iterations, int32_t iterations,
+                         float* rts, float* history, float* rmse, int32_t* status, const IcpPlaneWS& w,
+                         hipStream_t st) {
+  const dim3 gt((unsigned)w.icp.nblk, (unsigned)N);
+  for (int it = 0; it < iterations; ++it) {
+    if (int rc = search()) return rc;
+    if (int rc = launch(KID_NONE, "k_icp_plane_moments", k_icp_plane_moments, gt, MRR_BLOCK, 0, st, x, y, y_normals, P1, P2,
+                        x_lengths, y_lengths, (const double*)w.icp.xc, (const float*)rts, max_dist2,
+                        (const int32_t*)status, max_iterations, w.icp.key, w.icp.idx, w.prev, w.pmom, w.icp.nblk))
+      return rc;
+    if (int rc = launch(KID_NONE, "k_icp_plane_solve", k_icp_plane_solve, gt, MRR_BLOCK, 0, st, x, y, y_normals, N, P1, P2,
+                        x_lengths, (const double*)w.icp.xc, (const double*)w.pmom, w.icp.nblk,
+                        (const int32_t*)w.icp.idx, (const float*)w.prev, (const int32_t*)status, max_iterations, rts,
+                        history, w.cnt, w.icp.res))
+      return rc;
+    if (int rc = launch(KID_NONE, "k_icp_plane_status", k_icp_plane_status, 1, MRR_BLOCK, 0, st, (const double*)w.icp.res,
+                        w.icp.nblk, N, (const double*)w.cnt, relative_rmse_thr, max_iterations, rmse, status))
+      return rc;
+  }
+  return MR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1100,12 +1282,6 @@ size_t mr_icp_workspace(int64_t N, int64_t P1, int64_t P2) {
   return carve_icp(nullptr, N, P1).bytes;
 }
 
-static int check_icp(const char* who, const float* x, int64_t N, int64_t P1, int64_t P2) {
-  if (int rc = check_sizes(who, N, P1, P2)) return rc;
-  if (!x) return set_err(MR_EINVAL, "%s: x is NULL", who);
-  return MR_OK;
-}
-
 int32_t mr_icp_init(const float* x, int64_t N, int64_t P1, int64_t P2, const int64_t* x_lengths, const float* R0,
                     const float* T0, const float* s0, float* rts, int32_t* status, void* ws, size_t ws_bytes,
                     void* stream) {
@@ -1125,34 +1301,35 @@ int32_t mr_icp_iterate(const float* x, const float* y, int64_t N, int64_t P1, in
                        const int64_t* y_lengths, int32_t flags, float relative_rmse_thr, int32_t max_iterations,
                        int32_t iterations, float* rts, float* history, float* rmse, int32_t* status, void* ws,
                        size_t ws_bytes, void* stream) {
-  if (int rc = check_icp("icp", x, N, P1, P2)) return rc;
-  if (flags & ~MR_ICP_ALL) return set_err(MR_EINVAL, "icp: unknown bits in flags");
-  if (max_iterations < 1 || iterations < 0 || (int64_t)max_iterations * N > (1ll << 40) / MRI_RTS)
-    return set_err(MR_EINVAL, "icp: max_iterations must be >= 1 (and the history addressable), iterations >= 0");
-  if (!y || !rts || !history || !rmse || !status || !ws) return set_err(MR_EINVAL, "icp: NULL pointer");
+  if (int rc = check_icp_iterate("icp", x, y, N, P1, P2, flags, max_iterations, iterations, rts, history, rmse, status, ws))
+    return rc;
   const IcpWS w = carve_icp(ws, N, P1);
   if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "icp workspace too small");
   const NNGeom g = nn_geom(N, P1, P2, MRI_WANT_GROUPS);
   if (g.groups[0] > 0x7fffffffll) return set_err(MR_EUNSUPPORTED, "icp: P1 * P2 is too large for one launch");
   const hipStream_t st = (hipStream_t)stream;
-  const dim3 gn((unsigned)g.groups[0], (unsigned)N), gt((unsigned)w.nblk, (unsigned)N);
-  for (int it = 0; it < iterations; ++it) {
-    if (int rc = launch(KID_NONE, "k_icp_nn", k_icp_nn, gn, MRN_BLOCK, 0, st, x, y, g, x_lengths, y_lengths, (const float*)rts,
-                        (const int32_t*)status, max_iterations, w.key))
-      return rc;
-    if (int rc = launch(KID_NONE, "k_icp_moments", k_icp_moments, gt, MRR_BLOCK, 0, st, x, y, P1, P2, x_lengths, y_lengths,
-                        (const float*)nullptr, (const double*)w.xc, (const int32_t*)status, max_iterations, w.key, w.idx,
-                        w.mom, w.nblk))
-      return rc;
-    if (int rc = launch(KID_NONE, "k_icp_solve", k_icp_solve, gt, MRR_BLOCK, 0, st, x, y, N, P1, P2, x_lengths,
-                        (const float*)nullptr, (const double*)w.xc, (const double*)w.mom, w.nblk, (const int32_t*)w.idx,
-                        flags, 1e-9, (const int32_t*)status, max_iterations, rts, history, w.res))
-      return rc;
-    if (int rc = launch(KID_NONE, "k_icp_status", k_icp_status, 1, MRR_BLOCK, 0, st, (const double*)w.res, w.nblk, N,
-                        (const double*)w.xc, 1e-9, relative_rmse_thr, max_iterations, rmse, status))
-      return rc;
-  }
-  return MR_OK;
+  const ScanSearch search{x, y, g, x_lengths, y_lengths, rts, status, max_iterations, w.key, st};
+  return icp_iterations(search, x, y, N, P1, P2, x_lengths, y_lengths, flags, relative_rmse_thr, max_iterations,
+                        iterations, rts, history, rmse, status, w, st);
+}
+
+int32_t mr_icp_iterate_grid(const float* x, const float* y, int64_t N, int64_t P1, int64_t P2, const int64_t* x_lengths,
+                            const int64_t* y_lengths, const void* grid, size_t grid_bytes, int32_t flags,
+                            float relative_rmse_thr, int32_t max_iterations, int32_t iterations, float* rts,
+                            float* history, float* rmse, int32_t* status, uint64_t* visited, void* ws, size_t ws_bytes,
+                            void* stream) {
+  if (int rc = check_icp_iterate("icp grid", x, y, N, P1, P2, flags, max_iterations, iterations, rts, history, rmse, status,
+                                 ws))
+    return rc;
+  GridBuf b;
+  if (int rc = check_icp_grid("icp grid", grid, grid_bytes, N, P2, b)) return rc;
+  const IcpWS w = carve_icp(ws, N, P1);
+  if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "icp grid: icp workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  const GridSearch search{x, N, P1, P2, x_lengths, y_lengths, b, rts, __builtin_inff(), status, max_iterations, w.key,
+                          (u64*)visited, st};
+  return icp_iterations(search, x, y, N, P1, P2, x_lengths, y_lengths, flags, relative_rmse_thr, max_iterations,
+                        iterations, rts, history, rmse, status, w, st);
 }
 
 int32_t mr_icp_transform(const float* x, int64_t N, int64_t P, const float* rts, float* out, void* stream) {
@@ -1171,37 +1348,36 @@ int32_t mr_icp_plane_iterate(const float* x, const float* y, const float* y_norm
                              const int64_t* x_lengths, const int64_t* y_lengths, float max_dist2,
                              float relative_rmse_thr, int32_t max_iterations, int32_t iterations, float* rts,
                              float* history, float* rmse, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = check_icp("icp plane", x, N, P1, P2)) return rc;
-  if (!(max_dist2 > 0.0f)) return set_err(MR_EINVAL, "icp plane: max_dist2 must be > 0 (+inf: no limit)");
-  if (max_iterations < 1 || iterations < 0 || (int64_t)max_iterations * N > (1ll << 40) / MRI_RTS)
-    return set_err(MR_EINVAL,
-                   "icp plane: max_iterations must be >= 1 (and the history addressable), iterations >= 0");
-  if (!y || !y_normals || !rts || !history || !rmse || !status || !ws)
-    return set_err(MR_EINVAL, "icp plane: NULL pointer");
+  if (int rc = check_icp_plane_iterate("icp plane", x, y, y_normals, N, P1, P2, max_dist2, max_iterations, iterations, rts,
+                                       history, rmse, status, ws))
+    return rc;
   const IcpPlaneWS w = carve_icp_plane(ws, N, P1);
   if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "icp plane workspace too small");
   const NNGeom g = nn_geom(N, P1, P2, MRI_WANT_GROUPS);
   if (g.groups[0] > 0x7fffffffll) return set_err(MR_EUNSUPPORTED, "icp plane: P1 * P2 is too large for one launch");
   const hipStream_t st = (hipStream_t)stream;
-  const dim3 gn((unsigned)g.groups[0], (unsigned)N), gt((unsigned)w.icp.nblk, (unsigned)N);
-  for (int it = 0; it < iterations; ++it) {
-    if (int rc = launch(KID_NONE, "k_icp_nn", k_icp_nn, gn, MRN_BLOCK, 0, st, x, y, g, x_lengths, y_lengths, (const float*)rts,
-                        (const int32_t*)status, max_iterations, w.icp.key))
-      return rc;
-    if (int rc = launch(KID_NONE, "k_icp_plane_moments", k_icp_plane_moments, gt, MRR_BLOCK, 0, st, x, y, y_normals, P1, P2,
-                        x_lengths, y_lengths, (const double*)w.icp.xc, (const float*)rts, max_dist2,
-                        (const int32_t*)status, max_iterations, w.icp.key, w.icp.idx, w.prev, w.pmom, w.icp.nblk))
-      return rc;
-    if (int rc = launch(KID_NONE, "k_icp_plane_solve", k_icp_plane_solve, gt, MRR_BLOCK, 0, st, x, y, y_normals, N, P1, P2,
-                        x_lengths, (const double*)w.icp.xc, (const double*)w.pmom, w.icp.nblk,
-                        (const int32_t*)w.icp.idx, (const float*)w.prev, (const int32_t*)status, max_iterations, rts,
-                        history, w.cnt, w.icp.res))
-      return rc;
-    if (int rc = launch(KID_NONE, "k_icp_plane_status", k_icp_plane_status, 1, MRR_BLOCK, 0, st, (const double*)w.icp.res,
-                        w.icp.nblk, N, (const double*)w.cnt, relative_rmse_thr, max_iterations, rmse, status))
-      return rc;
-  }
-  return MR_OK;
+  const ScanSearch search{x, y, g, x_lengths, y_lengths, rts, status, max_iterations, w.icp.key, st};
+  return icp_plane_iterations(search, x, y, y_normals, N, P1, P2, x_lengths, y_lengths, max_dist2, relative_rmse_thr,
+                              max_iterations, iterations, rts, history, rmse, status, w, st);
+}
+
+int32_t mr_icp_plane_iterate_grid(const float* x, const float* y, const float* y_normals, int64_t N, int64_t P1,
+                                  int64_t P2, const int64_t* x_lengths, const int64_t* y_lengths, const void* grid,
+                                  size_t grid_bytes, float max_dist2, float relative_rmse_thr, int32_t max_iterations,
+                                  int32_t iterations, float* rts, float* history, float* rmse, int32_t* status,
+                                  uint64_t* visited, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = check_icp_plane_iterate("icp plane grid", x, y, y_normals, N, P1, P2, max_dist2, max_iterations, iterations,
+                                       rts, history, rmse, status, ws))
+    return rc;
+  GridBuf b;
+  if (int rc = check_icp_grid("icp plane grid", grid, grid_bytes, N, P2, b)) return rc;
+  const IcpPlaneWS w = carve_icp_plane(ws, N, P1);
+  if (ws_bytes < w.bytes) return set_err(MR_EWORKSPACE, "icp plane grid: icp plane workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  const GridSearch search{x, N, P1, P2, x_lengths, y_lengths, b, rts, max_dist2, status, max_iterations, w.icp.key,
+                          (u64*)visited, st};
+  return icp_plane_iterations(search, x, y, y_normals, N, P1, P2, x_lengths, y_lengths, max_dist2, relative_rmse_thr,
+                              max_iterations, iterations, rts, history, rmse, status, w, st);
 }
 
 int32_t mr_icp_plane_solve_host(const double* A21, const double* b6, const float* rts_in, const double* c3,

@@ -1025,29 +1025,57 @@ def _icp_loop(xf, xl, N, P1, P2, init, max_iterations, status_batch, workspace_q
     return bool(done), iters, rmse, xt, rts, hist[:iters]
 
 
+def _icp_grid_args(who, grid, visited, N, P2):
+    """The checked grid arguments of icp / icp_plane: (grid, its size in bytes, visited)."""
+    if not torch.is_tensor(grid):
+        raise ValueError(f"{who}: grid is the buffer tensor of point_grid_build")
+    _require_cuda(grid, visited)
+    gb = _ws_size(_lib.load().mr_point_grid_bytes, N, P2)
+    if grid.dtype != torch.uint8 or grid.numel() != gb or gb == 0 or not grid.is_contiguous():
+        raise ValueError(f"{who}: the grid buffer was not built for a target batch of this shape")
+    if visited is not None and (visited.dtype != torch.int64 or visited.numel() != 1):
+        raise ValueError(f"{who}: visited must be one int64")
+    return grid, gb, visited
+
+
 def icp(x, y, x_lengths=None, y_lengths=None, init=None, max_iterations=100, relative_rmse_thr=1e-6, flags=0,
-        status_batch=None):
+        status_batch=None, grid=None, visited=None):
     """The ICP loop on the device (mr_icp_*): (converged, iterations run, rmse (N) or None, Xt (N,P1,3), rts (N,13),
     history (iterations,N,13)). ``init`` = (R (N,3,3), T (N,3), s (N)) or None. The host enqueues ``status_batch``
     iterations at a time (default ICP_STATUS_BATCH) and reads two status words between the batches; the results do
-    not depend on that size."""
+    not depend on that size.
+
+    ``grid`` = point_grid_build(y, y_lengths) runs every iteration's neighbour search through that index
+    (mr_icp_iterate_grid) with the same results bit for bit; ``visited`` (one int64 on the device, cleared by the
+    caller; only with a grid) gains the number of distances the iterations that ran evaluated. A grid of other
+    clouds of the same shape gives wrong correspondences, inside the target."""
     xf, yf, xl, yl, N, P1, P2 = _cloud_args(x, y, x_lengths, y_lengths, 2)
     L = _lib.load()
+    head = (ptr(xf), ptr(yf), N, P1, P2, ptr(xl), ptr(yl))
+    tail = (int(flags), float(relative_rmse_thr), int(max_iterations))
+    if grid is None:
+        if visited is not None:
+            raise ValueError("icp: visited counts the distances of a search through a grid")
 
-    def iterate(k, *state):
-        return L.mr_icp_iterate(ptr(xf), ptr(yf), N, P1, P2, ptr(xl), ptr(yl), int(flags), float(relative_rmse_thr),
-                                int(max_iterations), k, *state)
+        def iterate(k, *state):
+            return L.mr_icp_iterate(*head, *tail, k, *state)
+    else:
+        grid, gb, visited = _icp_grid_args("icp", grid, visited, N, P2)
+
+        def iterate(k, rts, hist, rmse, status, *ws):
+            return L.mr_icp_iterate_grid(*head, ptr(grid), gb, *tail, k, rts, hist, rmse, status, ptr(visited), *ws)
 
     return _icp_loop(xf, xl, N, P1, P2, init, max_iterations, status_batch, L.mr_icp_workspace, iterate)
 
 
 def icp_plane(x, y, y_normals, x_lengths=None, y_lengths=None, init=None, max_iterations=100, relative_rmse_thr=1e-6,
-              max_correspondence_distance=None, status_batch=None):
+              max_correspondence_distance=None, status_batch=None, grid=None, visited=None):
     """The point-to-plane ICP loop on the device (mr_icp_plane_iterate, whose rule include/mi355r.h states), shaped
     like ``icp``: (converged, iterations run, rmse (N) or None, Xt (N,P1,3), rts (N,13), history (iterations,N,13)).
     ``y_normals`` (N,P2,3) are read as float32 and used as given; ``max_correspondence_distance`` d (None: no limit)
     reaches the kernels as float32(d) * float32(d) rounded once to float32. The scale of ``init`` stays fixed. The
-    results do not depend on ``status_batch``."""
+    results do not depend on ``status_batch``. ``grid`` and ``visited`` as in ``icp`` (mr_icp_plane_iterate_grid);
+    through a grid, a source point's walk also ends where no unvisited cell can hold a target within d."""
     xf, yf, xl, yl, N, P1, P2 = _cloud_args(x, y, x_lengths, y_lengths, 2)
     if tuple(y_normals.shape) != tuple(yf.shape):
         raise ValueError("y_normals must have y's padded shape (N, P2, 3)")
@@ -1056,10 +1084,20 @@ def icp_plane(x, y, y_normals, x_lengths=None, y_lengths=None, init=None, max_it
     r2 = float("inf") if max_correspondence_distance is None else \
         float(np.float32(max_correspondence_distance) * np.float32(max_correspondence_distance))
     L = _lib.load()
+    head = (ptr(xf), ptr(yf), ptr(nf), N, P1, P2, ptr(xl), ptr(yl))
+    tail = (r2, float(relative_rmse_thr), int(max_iterations))
+    if grid is None:
+        if visited is not None:
+            raise ValueError("icp_plane: visited counts the distances of a search through a grid")
 
-    def iterate(k, *state):
-        return L.mr_icp_plane_iterate(ptr(xf), ptr(yf), ptr(nf), N, P1, P2, ptr(xl), ptr(yl), r2,
-                                      float(relative_rmse_thr), int(max_iterations), k, *state)
+        def iterate(k, *state):
+            return L.mr_icp_plane_iterate(*head, *tail, k, *state)
+    else:
+        grid, gb, visited = _icp_grid_args("icp_plane", grid, visited, N, P2)
+
+        def iterate(k, rts, hist, rmse, status, *ws):
+            return L.mr_icp_plane_iterate_grid(*head, ptr(grid), gb, *tail, k, rts, hist, rmse, status, ptr(visited),
+                                               *ws)
 
     return _icp_loop(xf, xl, N, P1, P2, init, max_iterations, status_batch, L.mr_icp_plane_workspace, iterate)
 

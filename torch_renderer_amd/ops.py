@@ -21,7 +21,9 @@ gradient there. Not differentiable.
 
 ``knn_points`` (K <= 32 nearest neighbours, csrc/mr_knn.hip; ``dists`` is differentiable) and ``knn_gather``.
 ``PointGrid`` (csrc/mr_grid.hip) is a uniform-grid index over the targets that ``knn_points(..., grid=)`` searches
-instead of scanning every target, with the same result bit for bit.
+instead of scanning every target, with the same result bit for bit. ``iterative_closest_point`` and
+``iterative_closest_point_to_plane`` take one in place of ``Y`` and search it in every iteration (k_icp_nn_grid of
+csrc/mr_points.hip), again with the same result bit for bit.
 
 ``ball_query`` (the first K neighbours inside a radius, any K, csrc/mr_ballquery.hip; ``dists`` is differentiable) and
 ``masked_gather``.
@@ -76,6 +78,16 @@ def _clouds_and_lengths(pc, who):
     return pc, None, None
 
 
+def _icp_target(Y, who):
+    """(padded (N,P2,D) tensor, host-side counts or None, lengths tensor or None, grid buffer or None) of an ICP
+    target: a tensor or a Pointclouds as ``_clouds_and_lengths`` reads them, or a PointGrid, which stands for the
+    points it was built from."""
+    if isinstance(Y, PointGrid):
+        padded, lengths, counts = Y.points()
+        return padded, counts, None if Y.full else lengths, Y.buffer
+    return (*_clouds_and_lengths(Y, who), None)
+
+
 def _refuse_grad(who, *ts):
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
         raise NotImplementedError(f"{who}: not differentiable (an input requires grad; call it under torch.no_grad() "
@@ -120,11 +132,16 @@ def iterative_closest_point(X, Y, init_transform=None, max_iterations: int = 100
     ``ICPSolution(converged, rmse (N,), Xt, RTs, t_history)``, ``len(t_history)`` being the iterations run.
 
     The loop runs on the device, four launches an iteration and no (N, P1, P2) matrix (kernels.icp, csrc/mr_points.hip);
-    the host reads two status words every few iterations. Deterministic; not differentiable."""
+    the host reads two status words every few iterations. Deterministic; not differentiable.
+
+    ``Y`` may be a ``PointGrid`` built from the target points (a tensor with optional lengths, or a Pointclouds): every
+    iteration then searches that index instead of scanning every target, and the solution is that of the call with the
+    points, bit for bit. A grid whose tensor has been freed or modified in place since the build raises ValueError.
+    Nothing routes automatically."""
     if verbose:
         raise NotImplementedError("iterative_closest_point: verbose=True is not built")
     Xt, xc, xl = _clouds_and_lengths(X, "iterative_closest_point")
-    Yt, yc, yl = _clouds_and_lengths(Y, "iterative_closest_point")
+    Yt, yc, yl, grid = _icp_target(Y, "iterative_closest_point")
     b, dim = Xt.shape[0], Xt.shape[2]
     if dim != Yt.shape[2] or b != Yt.shape[0]:
         raise ValueError("Point sets X and Y have to have the same number of batches and data dimensions.")
@@ -146,7 +163,7 @@ def iterative_closest_point(X, Y, init_transform=None, max_iterations: int = 100
     flags = (_lib.MR_ICP_ESTIMATE_SCALE if estimate_scale else 0) | \
         (_lib.MR_ICP_ALLOW_REFLECTION if allow_reflection else 0)
     converged, iters, rmse, xt, rts, hist = kernels.icp(Xt, Yt, xl, yl, init_transform, max_iterations,
-                                                        relative_rmse_thr, flags)
+                                                        relative_rmse_thr, flags, grid=grid)
     if isinstance(X, Pointclouds):
         xt = X.update_padded(xt)
     return ICPSolution(converged, rmse, xt, _split_rts(rts), [_split_rts(hist[i]) for i in range(iters)])
@@ -184,10 +201,15 @@ def iterative_closest_point_to_plane(X, Y, Y_normals=None, init_transform=None, 
 
     Four launches an iteration, no (N, P1, P2) matrix, the host reads two status words every few iterations
     (kernels.icp_plane, the k_icp_plane_* kernels of csrc/mr_points.hip). Rigid only, normals as given, a brute-force
-    neighbour scan, deterministic, not differentiable."""
+    neighbour scan, deterministic, not differentiable.
+
+    ``Y`` may be a ``PointGrid`` built from the target points, as in ``iterative_closest_point``: step 1 then searches
+    that index, and with ``max_correspondence_distance`` a source point's search ends where no unvisited cell can hold
+    a target within d. The solution is that of the call with the points, bit for bit; ``Y_normals`` has the padded
+    shape of the grid's points, and ``None`` estimates them from those points with the brute-force scan."""
     who = "iterative_closest_point_to_plane"
     Xt, xc, xl = _clouds_and_lengths(X, who)
-    Yt, yc, yl = _clouds_and_lengths(Y, who)
+    Yt, yc, yl, grid = _icp_target(Y, who)
     b, dim = Xt.shape[0], Xt.shape[2]
     if dim != Yt.shape[2] or b != Yt.shape[0]:
         raise ValueError("Point sets X and Y have to have the same number of batches and data dimensions.")
@@ -217,11 +239,12 @@ def iterative_closest_point_to_plane(X, Y, Y_normals=None, init_transform=None, 
         raise ValueError(f"{who}: a target cloud is empty where its source is not")
     if Y_normals is None:
         with torch.no_grad():
-            Y_normals = estimate_pointcloud_normals(Y, neighborhood_size)
+            Y_normals = estimate_pointcloud_normals(Y, neighborhood_size) if grid is None else \
+                _local_frames(Yt, yl, yc, neighborhood_size, True)[1][..., 0]
     _require_cuda(Xt, Yt, Y_normals, *(init_transform or ()))
     converged, iters, rmse, xt, rts, hist = kernels.icp_plane(Xt, Yt, Y_normals, xl, yl, init_transform,
                                                               max_iterations, relative_rmse_thr,
-                                                              max_correspondence_distance)
+                                                              max_correspondence_distance, grid=grid)
     if isinstance(X, Pointclouds):
         xt = X.update_padded(xt)
     return ICPSolution(converged, rmse, xt, _split_rts(rts), [_split_rts(hist[i]) for i in range(iters)])
@@ -410,7 +433,8 @@ def knn_gather(x, idx, lengths=None):
 
 class PointGrid:
     """A uniform-grid index over the clouds ``points`` (an (N,P,3) tensor with optional ``lengths`` (N,), or a
-    ``Pointclouds``, which brings its own lengths), for ``knn_points(p1, points, lengths2=lengths, grid=...)``. Built on
+    ``Pointclouds``, which brings its own lengths), for ``knn_points(p1, points, lengths2=lengths, grid=...)`` and, in
+    place of ``Y``, for ``iterative_closest_point`` and ``iterative_closest_point_to_plane``. Built on
     the device in four launches (kernels.point_grid_build, csrc/mr_grid.hip); with a tensor nothing synchronises, and
     build plus search capture into a HIP graph. It holds no gradient and keeps a copy of the coordinates, so it
     remembers what it was built from — the tensor's identity, ``_version`` and shape, and the lengths — and
@@ -425,11 +449,13 @@ class PointGrid:
         """What the grid is built from (host only): the padded tensor, by weak reference, with its version and shape;
         the lengths tensor; whether every cloud is known on the host to be full (a call without lengths2 then fits)."""
         self.full = lengths is None
+        self._counts = None
         if isinstance(points, Pointclouds):
             if lengths is not None:
                 raise ValueError("PointGrid: a Pointclouds brings its own lengths")
             cloud, points = points, points.points_padded()
-            self.full = all(c == points.shape[1] for c in cloud.counts())
+            self._counts = cloud.counts()
+            self.full = all(c == points.shape[1] for c in self._counts)
             lengths = cloud.num_points_per_cloud()
         if not torch.is_tensor(points) or points.dim() != 3:
             raise ValueError("PointGrid: points must be an (N, P, 3) tensor or a Pointclouds")
@@ -451,6 +477,19 @@ class PointGrid:
         if not same:
             raise ValueError("knn_points: the grid was not built with these lengths2; rebuild it with "
                              "PointGrid(p2, lengths2)")
+
+    def points(self):
+        """(padded (N,P,3) tensor, lengths (N,) or None, host-side counts or None) the grid was built from; the counts
+        where a ``Pointclouds`` supplied them. ValueError if the tensor has been freed, or it or the lengths were
+        modified in place since the build."""
+        p = self._ref()
+        if p is None:
+            raise ValueError("PointGrid: the tensor the grid was built from has been freed; rebuild the grid")
+        stale = p._version != self._version or tuple(p.shape) != self.shape
+        if stale or (self.lengths is not None and self.lengths._version != self._lengths_version):
+            raise ValueError("PointGrid: the points or lengths the grid was built from were modified in place since; "
+                             "rebuild the grid")
+        return p, self.lengths, None if self._counts is None else list(self._counts)
 
     def describe(self):
         """(dims (N,3) int32, origin_cell (N,4) = lo xyz and the cell size, max_cell_count (N,) int32) on the host.
@@ -645,10 +684,17 @@ def estimate_pointcloud_local_coord_frames(pointclouds, neighborhood_size: int =
     elif torch.is_tensor(pointclouds):
         if pointclouds.dim() != 3:
             raise ValueError("estimate_pointcloud_local_coord_frames: pointclouds must be an (N, P, 3) tensor")
-        points, lengths = pointclouds, None
-        counts = [points.shape[1]] * points.shape[0]
+        points, lengths, counts = pointclouds, None, None
     else:
         raise ValueError("estimate_pointcloud_local_coord_frames: pointclouds is an (N, P, 3) tensor or a Pointclouds")
+    return _local_frames(points, lengths, counts, neighborhood_size, disambiguate_directions)
+
+
+def _local_frames(points, lengths, counts, neighborhood_size, disambiguate_directions):
+    """estimate_pointcloud_local_coord_frames on a padded (N,P,3) tensor with its lengths (None: full clouds) and the
+    host-side counts (None: the padded size, or with lengths one read of them)."""
+    if counts is None:
+        counts = [points.shape[1]] * points.shape[0] if lengths is None else [int(v) for v in lengths.tolist()]
     if points.shape[2] != 3:
         raise ValueError("The pointclouds argument has to be of shape (minibatch, N, 3)")
     K = int(neighborhood_size)
