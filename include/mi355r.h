@@ -144,6 +144,11 @@ int32_t mr_version(void);
 /* sizeof of the ABI structs as compiled into the library (binding self-check):
  * 0 mr_view_t, 1 mr_raster_settings_t, 2 mr_shade_params_t, 3 mr_mesh_t; -1 otherwise. */
 int32_t mr_struct_size(int32_t which);
+/* Host only (no GPU): the pixels p0 .. p1 along an image axis of S1 pixels (S2 = the other side) whose centres
+ * can lie inside the NDC interval [lo, hi] — the rule behind the binning's tile rectangles and the rasters'
+ * candidate rectangles, run on the CPU from the kernels' own source. Pass the padded interval (bbox -/+
+ * sqrt(blur_radius)). The range is before any clip to a tile; p0 > p1 means no pixel. */
+int32_t mr_pixel_range(float lo, float hi, int32_t S1, int32_t S2, int32_t* p0, int32_t* p1);
 
 /* ---------------- PyTorch3D _C.rasterize_meshes boundary ---------------- */
 size_t mr_rasterize_meshes_workspace(int64_t num_meshes, int64_t total_faces, int32_t H, int32_t W,

@@ -92,6 +92,7 @@ _SIGS = [
     ("mr_last_error", ctypes.c_char_p, []),
     ("mr_version", _I32, []),
     ("mr_struct_size", _I32, [_I32]),
+    ("mr_pixel_range", _I32, [ctypes.c_float, ctypes.c_float, _I32, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
     ("mr_rasterize_meshes_workspace", _SZ, [_I64, _I64, _I32, _I32, _I32]),
     ("mr_rasterize_meshes", _I32, [_VP, _VP, _VP, _I64, _I64, ctypes.POINTER(MrRasterSettings), _VP, _VP, _VP,
                                    _VP, _VP, _SZ, _VP]),

@@ -122,25 +122,7 @@ MR_DEV void block_incl_sum4(const int (&v)[4], int (*part4)[16], int (&incl)[4],
   lds_barrier();  // part4 is reused by the next call
 }
 
-// Inverse of col_ndc/row_ndc (approximate, widened by 0.05 px; the raster
-// kernel repeats the exact per-pixel bbox test, so a superset is all we need).
-MR_DEV void ndc_range_to_pix(float lo, float hi, int S1, int S2, int& p0, int& p1) {
-  float range = 2.0f;
-  if (S1 > S2) range = ((float)S1 * range) / (float)S2;
-  const float off = range / 2.0f;
-  // i = ((ndc + off) * S1 - off) / range ; pixel = S1 - 1 - i
-  float i_hi = ((hi + off) * (float)S1 - off) / range;
-  float i_lo = ((lo + off) * (float)S1 - off) / range;
-  float pf0 = (float)(S1 - 1) - i_hi - 0.05f;  // inverse error is ~1e-4 px; 0.05 px is ample
-  float pf1 = (float)(S1 - 1) - i_lo + 0.05f;
-  pf0 = fminf(fmaxf(pf0, -2.0f), (float)S1 + 1.0f);
-  pf1 = fminf(fmaxf(pf1, -2.0f), (float)S1 + 1.0f);
-  p0 = (int)floorf(pf0);
-  p1 = (int)ceilf(pf1);
-  if (p0 < 0) p0 = 0;
-  if (p1 > S1 - 1) p1 = S1 - 1;
-}
-
+// The tiles of record r's pixel rectangle (ndc_range_to_pix, mr_common.h); false: invalid, or no pixel at all.
 MR_DEV bool rec_tiles(const SetupParams& P, const FaceRec& r, int& tx0, int& tx1, int& ty0, int& ty1) {
   if (!(r.flags & FR_VALID)) return false;
   int cx0, cx1, cy0, cy1;

@@ -120,6 +120,31 @@ MR_DEV float pix_to_ndc(int i, int S1, int S2) {
 MR_DEV float col_ndc(int xi, int H, int W) { return pix_to_ndc(W - 1 - xi, W, H); }
 MR_DEV float row_ndc(int yi, int H, int W) { return pix_to_ndc(H - 1 - yi, H, W); }
 
+// The pixels p0 .. p1 (along the axis of S1 pixels) whose centres can pass eval_face's bbox test for the padded
+// NDC interval [lo, hi]: the approximate inverse of col_ndc / row_ndc, in a coordinate where an integer is a
+// pixel centre. The exact test keeps a centre only if it lies inside [lo, hi], i.e. inside the continuous range
+// [pf0, pf1] up to the inverse's error (~1e-4 px at 4096 px); widened by 0.05 px that is ceil(pf0) .. floor(pf1).
+// Rounding inward still gives a superset of the exact decision, which every consumer repeats per pixel; rounding
+// outward would only add a column and a row on each side that the exact test can never keep. An interval between
+// two centres, or off the image, gives an empty range (p0 > p1): no tile, no pixel. Host + device: the one copy
+// behind the binning rectangles, the rasters' per-lane rectangles and mr_pixel_range.
+__host__ MR_DEV void ndc_range_to_pix(float lo, float hi, int S1, int S2, int& p0, int& p1) {
+  float range = 2.0f;
+  if (S1 > S2) range = ((float)S1 * range) / (float)S2;
+  const float off = range / 2.0f;
+  // i = ((ndc + off) * S1 - off) / range ; pixel = S1 - 1 - i
+  float i_hi = ((hi + off) * (float)S1 - off) / range;
+  float i_lo = ((lo + off) * (float)S1 - off) / range;
+  float pf0 = (float)(S1 - 1) - i_hi - 0.05f;  // inverse error is ~1e-4 px; 0.05 px is ample
+  float pf1 = (float)(S1 - 1) - i_lo + 0.05f;
+  pf0 = fminf(fmaxf(pf0, -2.0f), (float)S1 + 1.0f);
+  pf1 = fminf(fmaxf(pf1, -2.0f), (float)S1 + 1.0f);
+  p0 = (int)ceilf(pf0);
+  p1 = (int)floorf(pf1);
+  if (p0 < 0) p0 = 0;
+  if (p1 > S1 - 1) p1 = S1 - 1;
+}
+
 // geometry_utils.h EdgeFunctionForward: E(p, a, b)
 MR_DEV float edge_fn(float px, float py, float ax, float ay, float bx, float by) {
   return (px - ax) * (by - ay) - (py - ay) * (bx - ax);

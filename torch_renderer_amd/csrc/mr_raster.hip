@@ -187,6 +187,16 @@ int32_t mr_struct_size(int32_t which) {
   }
 }
 
+int32_t mr_pixel_range(float lo, float hi, int32_t S1, int32_t S2, int32_t* p0, int32_t* p1) {
+  if (!p0 || !p1) return set_err(MR_EINVAL, "mr_pixel_range: p0 / p1 is NULL");
+  if (S1 <= 0 || S2 <= 0) return set_err(MR_EINVAL, "image size must be positive (got %d x %d)", S1, S2);
+  int a, b;
+  ndc_range_to_pix(lo, hi, S1, S2, a, b);  // the kernels' own copy, compiled for the host
+  *p0 = a;
+  *p1 = b;
+  return MR_OK;
+}
+
 static int check_settings(const mr_raster_settings_t* s) {
   if (!s) return set_err(MR_EINVAL, "settings is NULL");
   if (s->H <= 0 || s->W <= 0) return set_err(MR_EINVAL, "image size must be positive (got %d x %d)", s->H, s->W);
