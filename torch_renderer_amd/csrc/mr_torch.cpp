@@ -26,23 +26,29 @@ using torch::autograd::variable_list;
 
 namespace {
 
-// The C ABI entry points this node calls, from the library _lib.py loaded.
+// The C ABI entry points this node calls, from the library _lib.py loaded: X(member of g_abi, function).
+// The one list: the struct, init() and the module's abi_functions (the names _lib.py looks up) expand from it.
+#define MR_ABI_FUNCTIONS(X)                                \
+  X(last_error, mr_last_error)                             \
+  X(workspace, mr_render_workspace)                        \
+  X(workspace_meshes, mr_render_workspace_meshes)          \
+  X(reshade, mr_render_reshade)                            \
+  X(forward_opencv, mr_render_forward_opencv)              \
+  X(forward_poses, mr_render_forward_poses)                \
+  X(backward_workspace, mr_render_backward_workspace)      \
+  X(backward, mr_render_backward)                          \
+  X(backward_opencv, mr_render_backward_opencv)            \
+  X(loss_workspace, mr_pose_loss_workspace)                \
+  X(loss_forward_grad, mr_pose_loss_forward_grad)          \
+  X(loss_scale, mr_pose_loss_scale)                        \
+  X(loss_backward, mr_pose_loss_backward)                  \
+  X(quat, mr_quaternion_to_matrix)                         \
+  X(quat_backward, mr_quaternion_to_matrix_backward)
+
 struct Abi {
-  decltype(&mr_last_error) last_error = nullptr;
-  decltype(&mr_render_workspace) workspace = nullptr;
-  decltype(&mr_render_workspace_meshes) workspace_meshes = nullptr;
-  decltype(&mr_render_reshade) reshade = nullptr;
-  decltype(&mr_render_forward_opencv) forward_opencv = nullptr;
-  decltype(&mr_render_forward_poses) forward_poses = nullptr;
-  decltype(&mr_render_backward_workspace) backward_workspace = nullptr;
-  decltype(&mr_render_backward) backward = nullptr;
-  decltype(&mr_render_backward_opencv) backward_opencv = nullptr;
-  decltype(&mr_pose_loss_workspace) loss_workspace = nullptr;
-  decltype(&mr_pose_loss_forward_grad) loss_forward_grad = nullptr;
-  decltype(&mr_pose_loss_scale) loss_scale = nullptr;
-  decltype(&mr_pose_loss_backward) loss_backward = nullptr;
-  decltype(&mr_quaternion_to_matrix) quat = nullptr;
-  decltype(&mr_quaternion_to_matrix_backward) quat_backward = nullptr;
+#define X(member, fn) decltype(&fn) member = nullptr;
+  MR_ABI_FUNCTIONS(X)
+#undef X
 } g_abi;
 
 // The torch current stream of t's device (the autograd engine sets the forward's stream for the backward).
@@ -439,21 +445,9 @@ void init(const std::unordered_map<std::string, int64_t>& fn) {
     TORCH_CHECK(it != fn.end() && it->second != 0, "mi355r: C ABI function ", name, " missing");
     return (void*)it->second;
   };
-  g_abi.last_error = (decltype(g_abi.last_error))get("mr_last_error");
-  g_abi.workspace = (decltype(g_abi.workspace))get("mr_render_workspace");
-  g_abi.workspace_meshes = (decltype(g_abi.workspace_meshes))get("mr_render_workspace_meshes");
-  g_abi.reshade = (decltype(g_abi.reshade))get("mr_render_reshade");
-  g_abi.forward_opencv = (decltype(g_abi.forward_opencv))get("mr_render_forward_opencv");
-  g_abi.forward_poses = (decltype(g_abi.forward_poses))get("mr_render_forward_poses");
-  g_abi.backward_workspace = (decltype(g_abi.backward_workspace))get("mr_render_backward_workspace");
-  g_abi.backward = (decltype(g_abi.backward))get("mr_render_backward");
-  g_abi.backward_opencv = (decltype(g_abi.backward_opencv))get("mr_render_backward_opencv");
-  g_abi.loss_workspace = (decltype(g_abi.loss_workspace))get("mr_pose_loss_workspace");
-  g_abi.loss_forward_grad = (decltype(g_abi.loss_forward_grad))get("mr_pose_loss_forward_grad");
-  g_abi.loss_scale = (decltype(g_abi.loss_scale))get("mr_pose_loss_scale");
-  g_abi.loss_backward = (decltype(g_abi.loss_backward))get("mr_pose_loss_backward");
-  g_abi.quat = (decltype(g_abi.quat))get("mr_quaternion_to_matrix");
-  g_abi.quat_backward = (decltype(g_abi.quat_backward))get("mr_quaternion_to_matrix_backward");
+#define X(member, fn) g_abi.member = (decltype(g_abi.member))get(#fn);
+  MR_ABI_FUNCTIONS(X)
+#undef X
 }
 
 }  // namespace
@@ -468,7 +462,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // stale build instead of failing later on a missing symbol or a mismatched ABI
   m.attr("built_with_torch") = MR_TORCH_VERSION;
   m.attr("built_with_cxx11_abi") = (bool)_GLIBCXX_USE_CXX11_ABI;
-  m.def("init", &init, "the C ABI entry points (name -> address) of the loaded libmi355r.so");
+#define X(member, fn) #fn,
+  m.attr("abi_functions") = py::cast(std::vector<std::string>{MR_ABI_FUNCTIONS(X)});  // the keys init() wants
+#undef X
+  m.def("init", &init, "the C ABI entry points (name -> address, one per abi_functions) of the loaded libmi355r.so");
   m.def("render_views", &render_views, "fused render forward (+ autograd backward) through the C ABI");
   m.def("pose_loss", &pose_loss, "calc_loss with its gradients (+ autograd backward) through the C ABI");
   m.def("quaternion_to_matrix", &quaternion_to_matrix, "quaternion_to_matrix (+ autograd backward)");
