@@ -1,7 +1,8 @@
 """Per-workgroup timeline of k_bin_view on the C5 render (mesh_deformer.py:197: one view of the F=81,920 sphere at
 1024x1024, AmbientLights, TexturesVertex), from an experiment build with workgroup stamps:
 python tools/build_variant.py bvstamp -DMR_XP_BV_STAMP, then (GPU)
-MI355R_LIB=exp/bvstamp.so python tools/binview_stamps.py [--fragments]   (--fragments: the fragment pass's launch)
+MI355R_LIB=exp/bvstamp.so python tools/binview_stamps.py [--fragments | --headline]   (--fragments: the fragment
+pass's launch; --headline: the launch of bench.py's 64-view render step)
 Roles: binning (one workgroup per band of tile rows), ShadeRec packing, background fill. The launch's span is
 the last end minus the first start; each role's start / end spread says which one is the critical path."""
 import ctypes
@@ -33,8 +34,19 @@ def run_fragments(dev):
     torch.cuda.synchronize()
 
 
+def run_headline():
+    """The headline step of bench.py (cow, 512x512, 64 views, fwd+bwd: k_bin_view<1, 3>), a few graph replays."""
+    import bench
+    sys.argv = ["bench.py", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--no-fragment-pass", "--no-secondary"]
+    bench.main()
+    torch.cuda.synchronize()
+
+
 def main():
     dev = torch.device("cuda:0")
+    if "--headline" in sys.argv:  # (--headline: the 64-view render step's launch)
+        run_headline()
+        return report()
     if "--fragments" in sys.argv:
         run_fragments(dev)
         return report()

@@ -470,6 +470,55 @@ MR_DEV void fill_chunk_render_lc(const FwdParams& P, const Bg& b, int n, int c, 
   }
 }
 
+// Pacing of the background loops that run beside other work (k_bin_view's background workgroups,
+// k_tile_raster's chunks): before a wave issues a chunk it waits until at most MR_BG_INFLIGHT - 1 chunks'
+// stores are still outstanding (0: no wait). A wave's vmcnt holds 63, more than all the stores of its share,
+// so unpaced the whole background is queued in the launch's first microsecond.
+// Measured (profiles/bg_pacing_ab.txt): a cap of 1, 2, 4 or 8 chunks leaves the step, k_bin_view and
+// k_tile_raster where they are, so the loops ship unpaced (0). The background workgroups of k_bin_view end
+// at 35 us at any cap (183 MB at 5.2 TB/s, the store ceiling) and the binning workgroups, which the flood does
+// slow (scan + allocation 6.1 -> 3.9 us at a cap of 4), end at 26 us either way: they are not the launch's
+// critical path. Nor does a cap of 2 change the raster that interleaves its background (BGQ below).
+// Pacing only: no result depends on the wait. The count is that of the 16-B store path (5 store instructions
+// per render chunk with CH = 3, 7 per fragment chunk); an output set with fewer stores per chunk is paced
+// tighter, one with more looser.
+#ifndef MR_BG_INFLIGHT
+#define MR_BG_INFLIGHT 0
+#endif
+template <int MODE>
+MR_DEV void bg_pace() {
+  constexpr int cap = MR_BG_INFLIGHT;
+  if (cap > 0) {
+    constexpr int n = (MODE == 0 ? 7 : 5) * (cap > 0 ? cap - 1 : 0);
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n < 63 ? n : 63) : "memory");
+  }
+}
+
+// One chunk of the drop-in output set (depth + silhouette + RGB with CH = 3, W % 4 == 0, no pix_to_face, no
+// RGBA silhouette; bg_static_outputs): five 16-B stores with no branch on the output flags or on the lane. A
+// lane past the view's last quad (a partial last chunk) stores to that last quad instead: the same values at
+// an address a lower lane of the same instruction writes too (the background is the same for every pixel).
+MR_DEV void fill_chunk_static(const FwdParams& P, const Bg& b, int n, int c) {
+  const int lane = threadIdx.x & 63;
+  const int64_t HW = (int64_t)P.H * P.W;
+  const int64_t gi = (int64_t)c * 64 + lane, g = gi < HW / 4 ? gi : HW / 4 - 1;
+  const int64_t pix = (int64_t)n * HW + 4 * g;
+  *(float4*)(P.depth + pix) = make_float4(b.d, b.d, b.d, b.d);
+  *(float4*)(P.sil + pix) = make_float4(b.s, b.s, b.s, b.s);
+  float4* q = (float4*)(P.rgb + pix * 3);  // 4 pixels x 3 channels = 3 aligned 16-B stores (as fill_chunk)
+  float r0 = b.c[0], g0 = b.c[1], b0 = b.c[2], r1 = r0, g1 = g0, b1 = b0, r2 = r0, g2 = g0, b2 = b0;
+  asm volatile("" : "+v"(r1), "+v"(g1), "+v"(b1), "+v"(r2), "+v"(g2), "+v"(b2));
+  q[0] = make_float4(r0, g0, b0, r1);
+  q[1] = make_float4(g1, b1, r2, g2);
+  q[2] = make_float4(b2, r0, g0, b0);
+}
+// The output set fill_chunk_static writes (FwdParams of a MODE 1, CH = 3 launch). out_flags is compared as a
+// whole, as k_shade_render's specialisation does: a call whose flags carry more than the three outputs (a
+// ShadeRec slot other than 0, MR_OUT_ZBUF, ...) keeps the general writer and the old order, with the same results.
+static inline bool bg_static_outputs(const FwdParams& P) {
+  return P.out_flags == (MR_OUT_DEPTH | MR_OUT_SIL | MR_OUT_RGB) && !P.p2f32 && (P.W & 3) == 0;
+}
+
 template <int MODE, int CH>
 __global__ void __launch_bounds__(256) k_fill(FwdParams P) {
   const int gw = blockIdx.x * 4 + (threadIdx.x >> 6), G = gridDim.x * 4;
@@ -530,6 +579,7 @@ __global__ void __launch_bounds__(1024) k_bin_view(ViewBinParams P, FwdParams F)
   int cn = c0 / cpv, cc = c0 - cn * cpv;
 #pragma unroll 1
   for (int c = c0; c < F.fill_first; c += nbw) {
+    bg_pace<MODE>();
     fill_chunk<MODE, CH>(F, bg, cn, cc, vec);
     cn += gn;
     cc += gc;
@@ -562,7 +612,22 @@ __attribute__((noinline)) __device__ void raster_pair_rect(const FaceRec* __rest
 #ifndef MR_RASTER_WAVES
 #define MR_RASTER_WAVES 4  // waves / SIMD: 5 -> <= 96 VGPRs, 4 -> <= 128
 #endif
-template <int MODE, int CH, bool CLIP>
+// BGQ (MR_TR_BG_INTERLEAVE: the render with the output set of bg_static_outputs and no near-plane clipping,
+// chosen on the host): while the wave has background chunks left it writes one, with fill_chunk_static, after
+// each unit's pipeline advance; the chunks still left after its units, and all chunks of a wave without units,
+// go through the loop after the units as elsewhere. Every other instantiation is the loop it was (same
+// instructions).
+// Measured (profiles/bg_pacing_ab.txt): k_tile_raster 49.8 - 51.2 us against the parent's 52.4 - 54.7, the step
+// 192.5 - 194.1 against 196.9 - 200.2 us. One chunk per unit is the most that pays: two or four per unit (the
+// headline has two chunks per unit) measured 53.1 - 55.4 us.
+// The wave waits vmcnt(0) where the next unit first reads its prefetched records (the record is a phi of the
+// prefetched registers and an overflow unit's in-loop loads, consumed after the join), and the shared-tile merge
+// drains its atomics with vmcnt(0): a wave stops at each unit's start until its own background stores have
+// retired. Five stores per unit are cheap to wait for, ten or twenty are not.
+#ifndef MR_TR_BG_INTERLEAVE
+#define MR_TR_BG_INTERLEAVE 1
+#endif
+template <int MODE, int CH, bool CLIP, bool BGQ = false>
 __global__ void __launch_bounds__(256, MR_RASTER_WAVES) k_tile_raster(FwdParams P) {
   __shared__ WaveStage stage[4];
   const int lane = threadIdx.x & 63;
@@ -575,7 +640,8 @@ __global__ void __launch_bounds__(256, MR_RASTER_WAVES) k_tile_raster(FwdParams 
   const int H = P.H, W = P.W;
   // background chunks of this wave: c = gw, gw + G, ... < N * cpv, written after its units (the
   // waves that finish their raster work early stream the background while the others still run;
-  // chunks interleaved with the units measured 3 us slower, all chunks before them 20 us slower)
+  // a share of the chunks after every unit measured 3 us slower, all chunks before the units 20 us
+  // slower; BGQ: one chunk after each unit first)
   const int gw = blockIdx.x * 4 + wave, G = gridDim.x * 4;
   const bool vec = (W & 3) == 0;
   const int64_t HW = (int64_t)H * W * (MODE == 0 ? P.K : 1);
@@ -598,6 +664,7 @@ __global__ void __launch_bounds__(256, MR_RASTER_WAVES) k_tile_raster(FwdParams 
     if (MODE == 0 && P.emit_frag) {
 #pragma unroll 1
       for (; chunk < nchunks; chunk += G) {
+        bg_pace<MODE>();
         fill_frag_unlisted(P, cn, cc);
         cn += gn;
         cc += gc;
@@ -606,6 +673,7 @@ __global__ void __launch_bounds__(256, MR_RASTER_WAVES) k_tile_raster(FwdParams 
     } else {
 #pragma unroll 1
       for (; chunk < nchunks; chunk += G) {
+        bg_pace<MODE>();
         fill_chunk<MODE, CH>(P, bg, cn, cc, vec);
         cn += gn;
         cc += gc;
@@ -629,6 +697,14 @@ __global__ void __launch_bounds__(256, MR_RASTER_WAVES) k_tile_raster(FwdParams 
   // used when the unit / entry exists (guarded loads become branches whose phi copies wait on
   // the load at once), and the unit records travel as per-lane copies made uniform where they
   // are consumed (a uniform load is otherwise scalarised: load + readfirstlane + wait at issue).
+  // BGQ: (view, chunk in the view) of `chunk` and of the stride G, stepped with it
+  int qn = 0, qc = 0, qgn = 0, qgc = 0;
+  if constexpr (BGQ) {
+    qn = chunk / cpv;
+    qc = chunk - qn * cpv;
+    qgn = G / cpv;
+    qgc = G - qgn * cpv;
+  }
   const int lz = lane_zero();
   const int ulast = max(ue - 1, 0);
   int4 U1v = P.units[min(ub + jw, ulast) + lz];
@@ -711,6 +787,15 @@ __global__ void __launch_bounds__(256, MR_RASTER_WAVES) k_tile_raster(FwdParams 
         id2 = P.list[(u + 2 * Gp < ue && U3v.y >= 0 && lane < U3v.z) ? U3v.y + lane : 0];
         U2v = U3v;
         U3v = P.units[min(u + 3 * Gp, ulast) + lz];
+        if constexpr (BGQ) {
+          if (chunk < nchunks) {  // one background chunk beside this unit (uniform branch)
+            fill_chunk_static(P, bg, qn, qc);
+            chunk += G;
+            qn += qgn;
+            qc += qgc;
+            if (qc >= cpv) { qc -= cpv; ++qn; }
+          }
+        }
       }
       // candidate numbering: a DPP prefix sum over the masks' popcounts
       const int np = __popcll(cmask);
@@ -1168,9 +1253,19 @@ static int launch_raster_and_shade(FwdParams P, const BinGeom& g, int64_t N, hip
     if (int rc = launch(KID_UNIT_ORDER, "k_unit_order", k_unit_order, 8, 1024, 0, st, P.units, P.ctr, P.units_ws2)) return rc;
     P.units = P.units_ws2;
   }
-  if (int rc = launch(KID_TILE_RASTER, "k_tile_raster", clip ? k_tile_raster<MODE, CH, true> : k_tile_raster<MODE, CH, false>,
-                      clip ? rgrid_c : rgrid, 256, 0, st, P))
-    return rc;
+  auto raster = clip ? k_tile_raster<MODE, CH, true> : k_tile_raster<MODE, CH, false>;
+  int grid = clip ? rgrid_c : rgrid;
+  if constexpr (MODE == 1 && CH == 3 && MR_TR_BG_INTERLEAVE != 0) {
+    // the drop-in output set without near-plane clipping: background chunks interleaved with the units (BGQ;
+    // the CLIP instantiation would spill: it fills its 128 VGPRs already)
+    if (!clip && bg_static_outputs(P)) {
+      static int qgrid = 0;
+      if (!qgrid) qgrid = resident_grid(k_tile_raster<1, 3, false, true>, 256, 7);
+      raster = k_tile_raster<1, 3, false, true>;
+      grid = qgrid;
+    }
+  }
+  if (int rc = launch(KID_TILE_RASTER, "k_tile_raster", raster, grid, 256, 0, st, P)) return rc;
   if (MODE == 0 && P.emit_frag) return MR_OK;  // the raster wrote the listed tiles' fragments
   const int64_t slots_cap = N * (int64_t)g.T;
   if (MODE == 1 && MR_SHADE_RENDER) return launch_shade_render<CH>(P, slots_cap, st);
