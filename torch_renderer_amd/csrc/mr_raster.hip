@@ -57,11 +57,13 @@ TimingPool g_t;
 static const char* const kKernelNames[KID_COUNT] = {MR_KERNEL_IDS(MR_KID_NAME)};
 #undef MR_KID_NAME
 
-// Background chunks per wave of k_bin_view's background workgroups (measured on the bench
-// workloads, profiles/r2e_bg_ab.txt): beyond these the stores slow the view workgroups' binning
-// more than they shorten the raster.
+// Background chunks per wave of k_bin_view's background workgroups: the split of the background between the
+// binning launch, whose background workgroups set its span (a store stream at its ceiling), and k_tile_raster,
+// which hides its chunks beside its units. Render, headline step: 8 chunks per wave make k_bin_view 10 us shorter
+// and k_tile_raster 6.5 us longer than 12 do; 6 and 10 are both slower than 8, 16 by far; the pose and C5 steps do
+// not move (profiles/cover_rect_ab.txt; the history of both constants is in DESIGN.md section 8).
 #ifndef MR_BG_CPW_RENDER
-#define MR_BG_CPW_RENDER 12  // 5 KB chunks (depth, silhouette, RGB); 8 -> 12: render 259.0k -> 260.4k, 260.7k -> 263.1k frames/s (profiles/r4k_ab.txt)
+#define MR_BG_CPW_RENDER 8  // 5 KB chunks (depth, silhouette, RGB)
 #endif
 #ifndef MR_BG_CPW_FRAG
 #define MR_BG_CPW_FRAG 8    // 7 KB chunks (PyTorch3D fragments; 4 -> 8: fragment pass 166 -> 162 us)
