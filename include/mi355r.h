@@ -920,6 +920,38 @@ int32_t mr_icp_plane_iterate_grid(const float* x, const float* y, const float* y
                                   int32_t iterations, float* rts, float* history, float* rmse, int32_t* status,
                                   uint64_t* visited, void* ws, size_t ws_bytes, void* stream);
 
+/* Local frames and radius neighbourhoods through a point grid.
+ *
+ * mr_point_frames_grid is mr_point_frames, bit for bit in curvatures, frames and cov, with `grid` (a buffer of
+ * mr_point_grid_build for these points and lengths, grid_bytes >= mr_point_grid_bytes(N, P)) and `visited` added: the
+ * cloud is searched against itself through its own grid. One launch, a query per lane: the lane takes entry j of its
+ * cloud's cell-ordered targets as its query (so a wave's lanes walk neighbouring cells), walks the rings as
+ * mr_knn_points_grid does until its K-th distance is strictly below the ring bound, which leaves the K smallest
+ * (distance, index) keys the brute-force scan leaves, and sums and solves in that list's order; lanes j >= lengths[n]
+ * write the zero rows j. No index, neighbour or key goes to memory; the workspace is not used but must be given. The
+ * checks are mr_point_frames' (2 <= K <= 64, P > K, flags), then a NULL grid (MR_EINVAL) and the sizes of the grid buffer
+ * and the workspace (MR_EWORKSPACE, "too small"), all before any GPU call. A grid of other clouds of the same shape
+ * gives wrong frames and, because the output row of a lane is the index its grid entry stores (clamped to P - 1), may
+ * leave rows unwritten; every address stays in range.
+ *
+ * mr_ball_query_grid is mr_ball_query, bit for bit in dists and idx, for 1 <= K <= 64 (MR_EUNSUPPORTED above), with
+ * `grid` built from these p2 and lengths2, and `visited`. One launch, a query per lane: a target is a hit iff its
+ * float32 squared distance is < r2 = radius * radius (strict), and a hit enters the lane's ascending list on the key
+ * (index << 32 | distance bits), so the list ends as the K lowest-indexed hits. Cells are visited in no index order, so
+ * a full list stops nothing: the walk ends after ring r >= 1 once ((r - 2^-6) h)^2 (1 - 2^-18) > r2, when no target
+ * beyond the rings can be a hit, or when the rings cover the grid. A small radius in a large cloud visits a few cells;
+ * a radius of the cloud's size visits all of it, one query per lane, and loses to mr_ball_query. The gradient is
+ * mr_ball_query_backward, which reads only idx. `visited` as in mr_knn_points_grid; nothing read from `grid` is trusted
+ * for addressing (idx stays in [-1, P2)). The *_workspace functions return 256, or 0 out of range (K included). */
+size_t mr_point_frames_grid_workspace(int64_t N, int64_t P, int32_t K);
+int32_t mr_point_frames_grid(const float* points, int64_t N, int64_t P, const int64_t* lengths, const void* grid,
+                             size_t grid_bytes, int32_t K, int32_t flags, float* curvatures, float* frames, float* cov,
+                             uint64_t* visited, void* ws, size_t ws_bytes, void* stream);
+size_t mr_ball_query_grid_workspace(int64_t N, int64_t P1, int64_t P2, int32_t K);
+int32_t mr_ball_query_grid(const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2, const int64_t* lengths1,
+                           const int64_t* lengths2, const void* grid, size_t grid_bytes, float radius, int32_t K,
+                           float* dists, int32_t* idx, uint64_t* visited, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
-// mi355r — Radius neighbourhoods of point clouds (PyTorch3D ball_query): mr_ball_query / mr_ball_query_geometry of
-// include/mi355r.h. (mr_ball_query_backward is mr_knn.hip's neighbour_backward at norm 2.)
+// mi355r — Radius neighbourhoods of point clouds (PyTorch3D ball_query): mr_ball_query / mr_ball_query_geometry /
+// mr_ball_query_grid of include/mi355r.h. (mr_ball_query_backward is mr_knn.hip's neighbour_backward at norm 2.)
 //
 //   k_ball<Q, MODE>  a workgroup owns a tile of queries (Q per thread: mr_knn.h's scan_tile, the query load and the
 //                    staging of mr_cloud.h's scan) and walks a range of its cloud's targets in ascending LDS chunks.
@@ -17,6 +17,8 @@
 //                    capped at K: (N, splits, P1) int32 of workspace. The writing pass starts a split at the sum of
 //                    the earlier splits' counts, rescans only while that is below K for some lane, and the last split
 //                    pads. Index order is kept, so the result is bitwise that of MODE 0.
+//   k_ball_query_grid<KB>  mr_ball_query_grid, K <= 64: one query per lane walks a point grid of the targets (mr_grid.h's
+//                    grid_walk in its BALL form) and keeps its K lowest-indexed hits in registers: the same bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -24,8 +26,10 @@
 #include "mr_host.h"
 #include "mr_cloud.h"
 #include "mr_knn.h"
+#include "mr_grid.h"
 
 #define MRB_STRIDE 32  // targets between two tests of "is the wave full"
+#define MRB_GRID_MAXK 64  // the deepest list k_ball_query_grid keeps
 
 namespace {
 
@@ -123,6 +127,51 @@ __global__ void __launch_bounds__(MRN_BLOCK) k_ball(const float* __restrict__ p1
   }
 }
 
+// grid (blocks over P1, N), one wave a workgroup: mr_ball_query's result through a point grid of the targets
+// (mr_grid.h). One query per lane; a hit (d < r2, strict) enters the lane's ascending list on ball_key, index first,
+// so the list ends as the K lowest-indexed hits: the first K in index order. Candidates arrive in no index order and
+// a full list stops nothing; the walk ends after ring r >= 1 once ring_bound(r) > r2 (every target beyond the rings
+// is then at a distance >= the bound > r2 and cannot be a hit) or when the rings cover the grid.
+template <int KB>
+__global__ void __launch_bounds__(MRG_QBLOCK) k_ball_query_grid(const float* __restrict__ p1, int64_t P1, int64_t P2,
+                                                                const int64_t* __restrict__ l1,
+                                                                const int64_t* __restrict__ l2, int64_t budget,
+                                                                const GridHead* __restrict__ heads,
+                                                                const uint32_t* __restrict__ cell_start,
+                                                                const float4* __restrict__ pts, float r2, int K,
+                                                                float* __restrict__ dists, int32_t* __restrict__ idx,
+                                                                u64* __restrict__ visited) {
+  const int64_t n = blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * MRG_QBLOCK + threadIdx.x;
+  const int64_t lq = cloud_len(l1, n, P1);
+  const uint32_t lt = (uint32_t)cloud_len(l2, n, P2);
+  const GridHead H = heads[n];
+  int gx, gy, gz;
+  head_dims(H, budget, gx, gy, gz);
+  u64 L[KB];
+#pragma unroll
+  for (int j = 0; j < KB; ++j) L[j] = ~0ull;
+  uint32_t seen = 0u;
+  if (i < lq && lt > 0u) {
+    const float* __restrict__ q = p1 + 3 * (n * P1 + i);
+    grid_walk<2, KB, true, true>(H, gx, gy, gz, cell_start + n * (budget + 1), pts + n * P2, lt, (uint32_t)(P2 - 1),
+                                 q[0], q[1], q[2], K, r2, L, seen);
+  }
+  if (i < P1) {
+    float* __restrict__ od = dists + (n * P1 + i) * K;
+    int32_t* __restrict__ oi = idx + (n * P1 + i) * K;
+#pragma unroll
+    for (int s = 0; s < KB; ++s) {
+      const bool ok = L[s] != ~0ull;  // a row past its length never walked
+      if (s < K) {
+        od[s] = ok ? __uint_as_float((uint32_t)L[s]) : 0.0f;
+        oi[s] = ok ? (int32_t)(L[s] >> 32) : -1;
+      }
+    }
+  }
+  if (visited) grid_count_visited(seen, visited);
+}
+
 int check_ball(const char* who, const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2, float radius,
                int32_t K) {
   if (int rc = check_sizes(who, N, P1, P2)) return rc;
@@ -175,6 +224,47 @@ int32_t mr_ball_query(const float* p1, const float* p2, int64_t N, int64_t P1, i
   return MRB_SCAN_Q(2);
 #undef MRB_SCAN_Q
 #undef MRB_SCAN
+}
+
+size_t mr_ball_query_grid_workspace(int64_t N, int64_t P1, int64_t P2, int32_t K) {
+  if (!sizes_ok(N, P1, P2) || K < 1 || K > MRB_GRID_MAXK) return 0;
+  return 256;  // nothing is kept between the lanes; never 0, which means "out of range"
+}
+
+int32_t mr_ball_query_grid(const float* p1, const float* p2, int64_t N, int64_t P1, int64_t P2, const int64_t* lengths1,
+                           const int64_t* lengths2, const void* grid, size_t grid_bytes, float radius, int32_t K,
+                           float* dists, int32_t* idx, uint64_t* visited, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = check_ball("ball query grid", p1, p2, N, P1, P2, radius, K)) return rc;
+  if (K > MRB_GRID_MAXK) return set_err(MR_EUNSUPPORTED, "ball query grid: K > %d is not built", MRB_GRID_MAXK);
+  if (!dists || !idx || !ws || !grid)
+    return set_err(MR_EINVAL, "ball query grid: dists / idx / grid / workspace is NULL");
+  const GridBuf b = carve_grid(grid, N, P2);
+  if (grid_bytes < b.bytes) return set_err(MR_EWORKSPACE, "ball query grid: grid buffer too small");
+  if (ws_bytes < mr_ball_query_grid_workspace(N, P1, P2, K))
+    return set_err(MR_EWORKSPACE, "ball query grid workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  const int64_t budget = grid_budget(P2);
+  const dim3 g((unsigned)ceil_div(P1, MRG_QBLOCK), (unsigned)N);
+  const float r2 = radius * radius;
+  const int k = K;
+  int kb = 1;
+  while (kb < K) kb *= 2;
+#define MRB_GRID(KB)                                                                                              \
+  case KB:                                                                                                        \
+    return launch(KID_NONE, "k_ball_query_grid", k_ball_query_grid<KB>, g, MRG_QBLOCK, 0, st, p1, P1, P2, lengths1, \
+                  lengths2, budget, (const GridHead*)b.head, (const uint32_t*)b.cell_start, (const float4*)b.pts, r2, \
+                  k, dists, idx, (u64*)visited)
+  switch (kb) {
+    MRB_GRID(1);
+    MRB_GRID(2);
+    MRB_GRID(4);
+    MRB_GRID(8);
+    MRB_GRID(16);
+    MRB_GRID(32);
+    default:
+      MRB_GRID(64);
+  }
+#undef MRB_GRID
 }
 
 }  // extern "C"

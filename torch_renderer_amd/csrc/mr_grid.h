@@ -1,5 +1,5 @@
-// mi355r — What the searches through a point grid (mr_grid.hip's k_knn_grid, mr_points.hip's k_icp_nn_grid) share, one
-// copy of each: the layout of the grid buffer (GridHead, grid_budget, carve_grid), the head as a search may use it
+// mi355r — What the searches through a point grid (mr_grid.hip's k_knn_grid, mr_points.hip's k_icp_nn_grid,
+// mr_normals.hip's k_frames_grid, mr_ballquery.hip's k_ball_query_grid) share, one copy of each: the layout of the grid buffer (GridHead, grid_budget, carve_grid), the head as a search may use it
 // (head_dims), a coordinate's cell (cell_axis), the lower bound on the distances beyond the rings (ring_bound), the visit
 // of a run of cells (visit_range) and the lane's walk over the cube rings around its query (grid_walk). mr_grid.hip
 // states the layout and builds the buffer.
@@ -70,19 +70,32 @@ template <int NORM> __device__ __forceinline__ float ring_bound(int r, float h) 
   return bound >= MRG_MIN_BOUND ? bound : 0.0f;
 }
 
-// Targets b .. e of the cell order (clamped to the cloud's lt) into the list; returns how many were evaluated.
-template <int NORM, int KB>
+// A radius search's key, (index << 32) | float bits of the distance: ascending keys are ascending indices, so the KB
+// smallest are the first KB hits in index order, which is ball_query's rule.
+__device__ __forceinline__ u64 ball_key(float dist, uint32_t index) {
+  return ((u64)index << 32) | (u64)__float_as_uint(dist);
+}
+
+// Targets b .. e of the cell order (clamped to the cloud's lt) into the list; returns how many were evaluated. BALL:
+// only a target whose distance is strictly below `cap` enters, on ball_key.
+template <int NORM, int KB, bool BALL>
 __device__ __forceinline__ uint32_t visit_range(const uint32_t* __restrict__ cs, int64_t cb, int64_t ce,
                                                 const float4* __restrict__ tp, uint32_t lt, uint32_t last, float qx,
-                                                float qy, float qz, u64 (&L)[KB]) {
+                                                float qy, float qz, float cap, u64 (&L)[KB]) {
   uint32_t b = cs[cb], e = cs[ce];
   b = b < lt ? b : lt;
   e = e < lt ? e : lt;
   for (uint32_t j = b; j < e; ++j) {
     const float4 t = tp[j];
     const uint32_t id = __float_as_uint(t.w);
-    const u64 key = nn_key(dist3<NORM>(qx, qy, qz, t), id < last ? id : last);
-    if (key < L[KB - 1]) knn_insert<KB>(L, key);
+    if (BALL) {
+      const float d = dist3<NORM>(qx, qy, qz, t);
+      const u64 key = ball_key(d, id < last ? id : last);
+      if (d < cap && key < L[KB - 1]) knn_insert<KB>(L, key);  // false for a nan distance
+    } else {
+      const u64 key = nn_key(dist3<NORM>(qx, qy, qz, t), id < last ? id : last);
+      if (key < L[KB - 1]) knn_insert<KB>(L, key);
+    }
   }
   return e > b ? e - b : 0u;
 }
@@ -93,10 +106,12 @@ __device__ __forceinline__ uint32_t visit_range(const uint32_t* __restrict__ cs,
 // walks cube rings r = 0, 1, .. around the query's own cell: per (z, y) row of a ring either the whole x run (one
 // range of targets) or the run's two end cells. After ring r >= 1 it stops once its K-th distance is strictly below
 // ring_bound(r) (a distance that is inf or a nan never is), or, with CAP, once ring_bound(r) > cap: no target beyond
-// the rings can then lie within `cap` (ring_bound's 0 never stops it), or when the rings cover the grid. `seen` gains
+// the rings can then lie within `cap` (ring_bound's 0 never stops it), or when the rings cover the grid. With BALL
+// (a radius search: visit_range says what enters) a full list stops nothing, since a later cell may hold a lower index:
+// only the CAP stop and the cover end the walk. `seen` gains
 // the number of distances evaluated: the caller's counter by reference and not a return value, which cost k_knn_grid
 // registers (KB = 8: 128 VGPRs against 69). Every address is clamped: visit_range says how.
-template <int NORM, int KB, bool CAP>
+template <int NORM, int KB, bool CAP, bool BALL = false>
 __device__ __forceinline__ void grid_walk(const GridHead& H, int gx, int gy, int gz, const uint32_t* cs,
                                           const float4* tp, uint32_t lt, uint32_t last, float qx, float qy, float qz,
                                           int K, float cap, u64 (&L)[KB], uint32_t& seen) {
@@ -116,21 +131,23 @@ __device__ __forceinline__ void grid_walk(const GridHead& H, int gx, int gy, int
         const int64_t row = ((int64_t)z * gy + y) * gx;
         const bool face = z == cz - r || z == cz + r || y == cy - r || y == cy + r;
         if (face) {  // the whole run of the row
-          seen += visit_range<NORM, KB>(cs, row + x0, row + x1 + 1, tp, lt, last, qx, qy, qz, L);
+          seen += visit_range<NORM, KB, BALL>(cs, row + x0, row + x1 + 1, tp, lt, last, qx, qy, qz, cap, L);
         } else {  // the run's interior belongs to nearer rings: its two end cells, where the grid has them
           if (cx - r >= 0)
-            seen += visit_range<NORM, KB>(cs, row + cx - r, row + cx - r + 1, tp, lt, last, qx, qy, qz, L);
+            seen += visit_range<NORM, KB, BALL>(cs, row + cx - r, row + cx - r + 1, tp, lt, last, qx, qy, qz, cap, L);
           if (cx + r <= gx - 1)
-            seen += visit_range<NORM, KB>(cs, row + cx + r, row + cx + r + 1, tp, lt, last, qx, qy, qz, L);
+            seen += visit_range<NORM, KB, BALL>(cs, row + cx + r, row + cx + r + 1, tp, lt, last, qx, qy, qz, cap, L);
         }
       }
     }
     if (r >= cover) break;
     if (r >= 1) {
-      u64 worst = L[KB - 1];
+      if (!BALL) {
+        u64 worst = L[KB - 1];
 #pragma unroll
-      for (int j = 0; j < KB - 1; ++j) worst = j == K - 1 ? L[j] : worst;
-      if (key_dist(worst) < ring_bound<NORM>(r, H.h)) break;  // an empty slot's distance bits are a nan: false
+        for (int j = 0; j < KB - 1; ++j) worst = j == K - 1 ? L[j] : worst;
+        if (key_dist(worst) < ring_bound<NORM>(r, H.h)) break;  // an empty slot's distance bits are a nan: false
+      }
       if (CAP && ring_bound<NORM>(r, H.h) > cap) break;
     }
   }

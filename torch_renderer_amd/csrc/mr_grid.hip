@@ -24,7 +24,8 @@
 //                  below ring_bound(r), a lower bound on the float32 distance of every target outside the rings
 //                  (DESIGN.md §3 "Point grid" has the argument), or when the rings cover the grid. The walk
 //                  (grid_walk), the buffer's layout and what else a search needs live in mr_grid.h, which
-//                  mr_points.hip's k_icp_nn_grid shares.
+//                  mr_points.hip's k_icp_nn_grid, mr_normals.hip's k_frames_grid and mr_ballquery.hip's
+//                  k_ball_query_grid share.
 // Nothing read from the grid buffer is trusted for addressing: dims are clamped and checked against the budget, target
 // ranges are clamped to the cloud's length and stored indices to P2 - 1.
 #include <hip/hip_runtime.h>

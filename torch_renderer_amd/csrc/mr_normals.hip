@@ -1,6 +1,6 @@
 // mi355r — Local coordinate frames of point clouds (PyTorch3D estimate_pointcloud_local_coord_frames /
-// estimate_pointcloud_normals, 2 <= K <= 64): mr_point_frames / mr_point_frames_geometry / mr_symmetric_eig3_host of
-// include/mi355r.h.
+// estimate_pointcloud_normals, 2 <= K <= 64): mr_point_frames / mr_point_frames_geometry / mr_point_frames_grid /
+// mr_symmetric_eig3_host of include/mi355r.h.
 //
 //   k_frames        k_knn's scan (mr_knn.h's knn_scan) of a cloud against itself: a workgroup owns a tile of queries
 //                   (Q per thread) and keeps every query's KB smallest (distance, index) keys ascending in registers,
@@ -12,7 +12,9 @@
 //                   query and split into the workspace, and one thread per query merges them by key and runs the same
 //                   frames_epilogue. The key order is total and the epilogue sums in list order, so the result does
 //                   not depend on the splits, bit for bit.
-//   sym_eig3        eigenvalues (ascending) and unit eigenvectors of a symmetric 3x3 in float32: the matrix is divided
+//   k_frames_grid   mr_point_frames_grid: one query per lane walks its cloud's point grid (mr_grid.h's grid_walk) to
+//                   the same list and runs the same frames_epilogue: one launch, no workspace, the same bits.
+//   sym_eig3       eigenvalues (ascending) and unit eigenvectors of a symmetric 3x3 in float32: the matrix is divided
 //                   by the sum of its diagonal's magnitudes (its trace, for a covariance), so the iteration sees the
 //                   same numbers at every scale of the cloud; MRF_SWEEPS cyclic Jacobi sweeps, the count fixed; host
 //                   and device run the same operations (no contraction, correctly rounded division and square root).
@@ -24,6 +26,7 @@
 #include "mr_host.h"
 #include "mr_cloud.h"
 #include "mr_knn.h"
+#include "mr_grid.h"
 
 #define MRF_MINK 2
 #define MRF_MAXK 64
@@ -280,6 +283,54 @@ __global__ void __launch_bounds__(MRK_TBLOCK) k_frames_merge(const float* __rest
                       cov ? cov + 6 * row : nullptr);
 }
 
+// grid (blocks over P, N), one wave a workgroup: k_frames' result through the cloud's own point grid (mr_grid.h). A
+// lane's query is entry j of its cloud's cell-ordered targets, so the lanes of a wave walk neighbouring cells (against
+// lane = point j: 136 us for 223 at 1 x 20,000, K = 16); its output row is the index stored beside the
+// coordinates, clamped as visit_range clamps it. grid_walk leaves the same KB smallest keys as knn_scan: the same
+// distance expression, the total key order, the point itself included; frames_epilogue sums in list order, so the
+// outputs are those of k_frames bit for bit. Lanes j >= length write the zero rows j. Nothing but the outputs goes to
+// memory. A stale grid (other clouds of the same shape) gives wrong frames and, two entries naming one row, may leave
+// rows unwritten; every address stays in range, which is all a stale grid is promised.
+template <int KB>
+__global__ void __launch_bounds__(MRG_QBLOCK) k_frames_grid(const float* __restrict__ pts, int64_t P,
+                                                            const int64_t* __restrict__ lens, int64_t budget,
+                                                            const GridHead* __restrict__ heads,
+                                                            const uint32_t* __restrict__ cell_start,
+                                                            const float4* __restrict__ gp, int K, int flags,
+                                                            float* __restrict__ cur, float* __restrict__ frm,
+                                                            float* __restrict__ cov, u64* __restrict__ visited) {
+  const int64_t n = blockIdx.y;
+  const int64_t j = (int64_t)blockIdx.x * MRG_QBLOCK + threadIdx.x;
+  const int64_t len = cloud_len(lens, n, P);
+  const float* __restrict__ cloud = pts + 3 * n * P;
+  const GridHead H = heads[n];
+  int gx, gy, gz;
+  head_dims(H, budget, gx, gy, gz);
+  u64 L[KB];
+#pragma unroll
+  for (int k = 0; k < KB; ++k) L[k] = ~0ull;
+  uint32_t seen = 0u;
+  const bool inside = j < len;
+  int64_t i = j;
+  float px = 0.0f, py = 0.0f, pz = 0.0f;
+  if (inside) {
+    const float4 t = gp[n * P + j];
+    const uint32_t id = __float_as_uint(t.w), last = (uint32_t)(P - 1);
+    i = id < last ? id : last;
+    px = t.x;
+    py = t.y;
+    pz = t.z;
+    grid_walk<2, KB, false>(H, gx, gy, gz, cell_start + n * (budget + 1), gp + n * P, (uint32_t)len, last, px, py, pz,
+                            K, 0.0f, L, seen);
+  }
+  if (j < P) {
+    const int64_t row = n * P + i;
+    frames_epilogue<KB>(L, inside, K, cloud, i, px, py, pz, flags, cur + 3 * row, frm + 9 * row,
+                        cov ? cov + 6 * row : nullptr);
+  }
+  if (visited) grid_count_visited(seen, visited);
+}
+
 int check_frames(const char* who, int64_t N, int64_t P, int32_t K) {
   if (int rc = check_sizes(who, N, P, P)) return rc;
   if (K < MRF_MINK) return set_err(MR_EINVAL, "%s: K must be >= %d", who, MRF_MINK);
@@ -348,6 +399,43 @@ int32_t mr_point_frames(const float* points, int64_t N, int64_t P, const int64_t
     MRF_MERGE(64);
   }
 #undef MRF_MERGE
+}
+
+size_t mr_point_frames_grid_workspace(int64_t N, int64_t P, int32_t K) {
+  if (!frames_args_ok(N, P, K)) return 0;
+  return 256;  // nothing is kept between the lanes; never 0, which means "out of range"
+}
+
+int32_t mr_point_frames_grid(const float* points, int64_t N, int64_t P, const int64_t* lengths, const void* grid,
+                             size_t grid_bytes, int32_t K, int32_t flags, float* curvatures, float* frames, float* cov,
+                             uint64_t* visited, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = check_frames("point frames grid", N, P, K)) return rc;
+  if (!points || !curvatures || !frames || !ws || !grid)
+    return set_err(MR_EINVAL, "point frames grid: points / curvatures / frames / grid / workspace is NULL");
+  if (flags & ~MR_FRAMES_DISAMBIGUATE) return set_err(MR_EINVAL, "point frames grid: unknown flags 0x%x", flags);
+  const GridBuf b = carve_grid(grid, N, P);
+  if (grid_bytes < b.bytes) return set_err(MR_EWORKSPACE, "point frames grid: grid buffer too small");
+  if (ws_bytes < mr_point_frames_grid_workspace(N, P, K))
+    return set_err(MR_EWORKSPACE, "point frames grid workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  const int64_t budget = grid_budget(P);
+  const dim3 g((unsigned)ceil_div(P, MRG_QBLOCK), (unsigned)N);
+  const int k = K, fl = flags;
+  int kb = MRF_MIN_BUCKET;
+  while (kb < K) kb *= 2;
+#define MRF_GRID(KB)                                                                                           \
+  case KB:                                                                                                     \
+    return launch(KID_NONE, "k_frames_grid", k_frames_grid<KB>, g, MRG_QBLOCK, 0, st, points, P, lengths, budget, \
+                  (const GridHead*)b.head, (const uint32_t*)b.cell_start, (const float4*)b.pts, k, fl, curvatures, \
+                  frames, cov, (u64*)visited)
+  switch (kb) {
+    MRF_GRID(8);
+    MRF_GRID(16);
+    MRF_GRID(32);
+    default:
+      MRF_GRID(64);
+  }
+#undef MRF_GRID
 }
 
 int32_t mr_symmetric_eig3_host(const float* cov, int64_t M, float* eigenvalues, float* eigenvectors) {

@@ -331,8 +331,8 @@ def _neighbour_forward(workspace, launch, scalar, p1f, p2f, l1, l2, N, P1, P2, K
 
 
 class _NeighbourDists(torch.autograd.Function):
-    """What KnnPoints, KnnPointsGrid and BallQuery are: a search ``_search(p1, p2, lengths1, lengths2, K, x, *more)``
-    (``more``: further arguments without a gradient, KnnPointsGrid's grid buffer) -> (dists, idx, the
+    """What KnnPoints, KnnPointsGrid, BallQuery and BallQueryGrid are: a search ``_search(p1, p2, lengths1, lengths2, K,
+    x, *more)`` (``more``: further arguments without a gradient, the grid buffer of the two grid classes) -> (dists, idx, the
     float32 clouds and int64 lengths it ran on, the checked K) with the gradient of ``dists`` w.r.t. p1 and p2 (``idx``
     is not differentiable): three launches backward and no memset, the many-to-one p2 side summed in fixed point, by
     the ``_backward`` entry point, which takes ``x`` as its norm if ``_pass_norm``."""
@@ -520,6 +520,47 @@ class BallQuery(_NeighbourDists):
     _search, _backward, _pass_norm = staticmethod(_ball_search), "mr_ball_query_backward", False
 
 
+BALL_GRID_MAX_K = 64
+
+
+def _ball_grid_search(p1, p2, lengths1, lengths2, K, radius, grid, visited=None):
+    K, radius = _ball_args(K, radius)
+    if K > BALL_GRID_MAX_K:
+        raise NotImplementedError(f"ball_query: K > {BALL_GRID_MAX_K} through a grid is not built")
+    p1f, p2f, l1, l2, N, P1, P2 = _cloud_args(p1, p2, lengths1, lengths2, 2)
+    if not torch.is_tensor(grid):
+        raise ValueError("ball_query: grid is the buffer tensor of point_grid_build")
+    _require_cuda(grid, visited)
+    L = _lib.load()
+    gb = _ws_size(L.mr_point_grid_bytes, N, P2)
+    if grid.dtype != torch.uint8 or grid.numel() != gb or gb == 0 or not grid.is_contiguous():
+        raise ValueError("ball_query: the grid buffer was not built for a target batch of this shape")
+    if visited is not None and (visited.dtype != torch.int64 or visited.numel() != 1):
+        raise ValueError("ball_query: visited must be one int64")
+    dev = p1f.device
+    dists = torch.empty((N, P1, K), device=dev)
+    idx = torch.empty((N, P1, K), dtype=torch.int32, device=dev)
+    ws, wsb = _workspace(L.mr_ball_query_grid_workspace, dev, N, P1, P2, K)
+    check(L.mr_ball_query_grid(ptr(p1f), ptr(p2f), N, P1, P2, ptr(l1), ptr(l2), ptr(grid), gb, radius, K, ptr(dists),
+                               ptr(idx), ptr(visited), ptr(ws), wsb, _lib.stream_handle(dev)))
+    return dists, idx, (p1f, p2f, l1, l2), K
+
+
+def ball_query_grid(p1, p2, grid, lengths1=None, lengths2=None, K=16, radius=0.2, visited=None):
+    """ball_query's (dists, idx), bit for bit, through ``grid`` = point_grid_build(p2, lengths2), for K <= 64: a query
+    visits the cells around its own in growing cube rings until no unvisited cell can hold a target inside the radius,
+    and keeps its K lowest-indexed hits. ``visited`` (one int64 on the device, cleared by the caller) gains the number
+    of distances evaluated. A grid of other clouds of the same shape gives wrong neighbours, idx still in [-1, P2). No
+    autograd; one launch (mr_ball_query_grid)."""
+    return _ball_grid_search(p1, p2, lengths1, lengths2, K, radius, grid, visited)[:2]
+
+
+class BallQueryGrid(_NeighbourDists):
+    """BallQuery with the forward search through a grid buffer, ``apply(p1, p2, lengths1, lengths2, K, radius, grid)``:
+    the same idx, so the same backward (mr_ball_query_backward)."""
+    _search, _backward, _pass_norm = staticmethod(_ball_grid_search), "mr_ball_query_backward", False
+
+
 # --------------------------------------------------------------------------- farthest points (csrc/mr_fps.hip)
 def farthest_geometry(N, P, Kmax):
     """(threads, points_per_thread, streamed) of the launch mr_farthest_points makes for these shapes (host only):
@@ -638,7 +679,7 @@ def symmetric_eig3_host(cov):
     return lam, vec
 
 
-def point_frames(points, lengths=None, K=50, disambiguate=True, return_cov=False):
+def point_frames(points, lengths=None, K=50, disambiguate=True, return_cov=False, grid=None, visited=None):
     """(curvatures (N,P,3), frames (N,P,3,3)[, cov (N,P,6)]) in float32, by the rule of mr_point_frames
     (include/mi355r.h): for every point i < lengths[n] of points (N,P,3), the covariance of its K nearest points of the
     same cloud (itself included; knn_points' distance and tie rule) about their mean, its eigenvalues ascending and
@@ -646,7 +687,12 @@ def point_frames(points, lengths=None, K=50, disambiguate=True, return_cov=False
     towards the majority of the neighbours and makes column 1 their cross product; otherwise every column's largest
     component is positive. ``cov`` is the covariance's upper triangle xx, xy, xz, yy, yz, zz. Rows past a length, and
     every row of a cloud shorter than K, are zeros; P <= K raises ValueError. 2 <= K <= 64. No autograd; one launch,
-    or a scan and a merge when the shapes alone cannot fill the chip; nothing synchronises."""
+    or a scan and a merge when the shapes alone cannot fill the chip; nothing synchronises.
+
+    ``grid`` = point_grid_build(points, lengths) searches every point's neighbourhood through that index instead
+    (mr_point_frames_grid, one launch): the same outputs bit for bit. ``visited`` (one int64 on the device, cleared by
+    the caller; only with a grid) gains the number of distances evaluated. A grid of other clouds of the same shape
+    gives wrong frames and may leave rows unwritten."""
     if points.dim() != 3:
         raise ValueError("point frames: points must be an (N, P, D) tensor")
     if points.shape[2] != 3:
@@ -657,16 +703,33 @@ def point_frames(points, lengths=None, K=50, disambiguate=True, return_cov=False
     K = _frames_k(K, P)
     if lengths is not None and tuple(lengths.shape) != (N,):
         raise ValueError("lengths must be of shape (N,)")
-    _require_cuda(points, lengths)
+    if grid is None:
+        if visited is not None:
+            raise ValueError("point frames: visited counts the distances of a search through a grid")
+    elif not torch.is_tensor(grid):
+        raise ValueError("point frames: grid is the buffer tensor of point_grid_build")
+    _require_cuda(points, lengths, grid, visited)
     pf = points.detach().float().contiguous()
     l = None if lengths is None else lengths.detach().to(torch.int64).contiguous()
     L = _lib.load()
+    if grid is not None:
+        gb = _ws_size(L.mr_point_grid_bytes, N, P)
+        if grid.dtype != torch.uint8 or grid.numel() != gb or gb == 0 or not grid.is_contiguous():
+            raise ValueError("point frames: the grid buffer was not built for a batch of this shape")
+        if visited is not None and (visited.dtype != torch.int64 or visited.numel() != 1):
+            raise ValueError("point frames: visited must be one int64")
     dev = pf.device
     cur, frm = torch.empty((N, P, 3), device=dev), torch.empty((N, P, 3, 3), device=dev)
     cov = torch.empty((N, P, 6), device=dev) if return_cov else None
-    ws, wsb = _workspace(L.mr_point_frames_workspace, dev, N, P, K)
-    check(L.mr_point_frames(ptr(pf), N, P, ptr(l), K, _lib.MR_FRAMES_DISAMBIGUATE if disambiguate else 0, ptr(cur),
-                            ptr(frm), ptr(cov), ptr(ws), wsb, _lib.stream_handle(dev)))
+    flags = _lib.MR_FRAMES_DISAMBIGUATE if disambiguate else 0
+    if grid is None:
+        ws, wsb = _workspace(L.mr_point_frames_workspace, dev, N, P, K)
+        check(L.mr_point_frames(ptr(pf), N, P, ptr(l), K, flags, ptr(cur), ptr(frm), ptr(cov), ptr(ws), wsb,
+                                _lib.stream_handle(dev)))
+    else:
+        ws, wsb = _workspace(L.mr_point_frames_grid_workspace, dev, N, P, K)
+        check(L.mr_point_frames_grid(ptr(pf), N, P, ptr(l), ptr(grid), gb, K, flags, ptr(cur), ptr(frm), ptr(cov),
+                                     ptr(visited), ptr(ws), wsb, _lib.stream_handle(dev)))
     return (cur, frm, cov) if return_cov else (cur, frm)
 
 

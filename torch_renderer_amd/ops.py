@@ -26,16 +26,18 @@ instead of scanning every target, with the same result bit for bit. ``iterative_
 csrc/mr_points.hip), again with the same result bit for bit.
 
 ``ball_query`` (the first K neighbours inside a radius, any K, csrc/mr_ballquery.hip; ``dists`` is differentiable) and
-``masked_gather``.
+``masked_gather``. ``ball_query(..., grid=PointGrid(p2))`` searches the index instead, K <= 64, bit for bit.
 
 ``sample_farthest_points`` (csrc/mr_fps.hip): one workgroup per cloud runs all K rounds on the device; the selected
 points are differentiable w.r.t. the input points.
 
 ``estimate_pointcloud_normals`` and ``estimate_pointcloud_local_coord_frames`` (csrc/mr_normals.hip): the K <= 64
-neighbourhood scan, the covariance and its 3x3 eigen solve in one launch. Not differentiable.
+neighbourhood scan, the covariance and its 3x3 eigen solve in one launch. Not differentiable. Both take a
+``PointGrid`` in place of the cloud and then search it (k_frames_grid), bit for bit.
 """
 from __future__ import annotations
 
+import inspect
 import warnings
 import weakref
 from typing import NamedTuple, Optional
@@ -206,7 +208,8 @@ def iterative_closest_point_to_plane(X, Y, Y_normals=None, init_transform=None, 
     ``Y`` may be a ``PointGrid`` built from the target points, as in ``iterative_closest_point``: step 1 then searches
     that index, and with ``max_correspondence_distance`` a source point's search ends where no unvisited cell can hold
     a target within d. The solution is that of the call with the points, bit for bit; ``Y_normals`` has the padded
-    shape of the grid's points, and ``None`` estimates them from those points with the brute-force scan."""
+    shape of the grid's points, and ``None`` estimates them from those points through the same grid (k_frames_grid),
+    bit for bit the normals of ``estimate_pointcloud_normals``."""
     who = "iterative_closest_point_to_plane"
     Xt, xc, xl = _clouds_and_lengths(X, who)
     Yt, yc, yl, grid = _icp_target(Y, who)
@@ -240,7 +243,7 @@ def iterative_closest_point_to_plane(X, Y, Y_normals=None, init_transform=None, 
     if Y_normals is None:
         with torch.no_grad():
             Y_normals = estimate_pointcloud_normals(Y, neighborhood_size) if grid is None else \
-                _local_frames(Yt, yl, yc, neighborhood_size, True)[1][..., 0]
+                _local_frames(Yt, yl, yc, neighborhood_size, True, grid)[1][..., 0]
     _require_cuda(Xt, Yt, Y_normals, *(init_transform or ()))
     converged, iters, rmse, xt, rts, hist = kernels.icp_plane(Xt, Yt, Y_normals, xl, yl, init_transform,
                                                               max_iterations, relative_rmse_thr,
@@ -433,8 +436,10 @@ def knn_gather(x, idx, lengths=None):
 
 class PointGrid:
     """A uniform-grid index over the clouds ``points`` (an (N,P,3) tensor with optional ``lengths`` (N,), or a
-    ``Pointclouds``, which brings its own lengths), for ``knn_points(p1, points, lengths2=lengths, grid=...)`` and, in
-    place of ``Y``, for ``iterative_closest_point`` and ``iterative_closest_point_to_plane``. Built on
+    ``Pointclouds``, which brings its own lengths), for ``knn_points(p1, points, lengths2=lengths, grid=...)`` and
+    ``ball_query(..., grid=...)``, in place of ``Y`` for ``iterative_closest_point`` and
+    ``iterative_closest_point_to_plane``, and in place of the cloud for ``estimate_pointcloud_normals`` and
+    ``estimate_pointcloud_local_coord_frames``. Built on
     the device in four launches (kernels.point_grid_build, csrc/mr_grid.hip); with a tensor nothing synchronises, and
     build plus search capture into a HIP graph. It holds no gradient and keeps a copy of the coordinates, so it
     remembers what it was built from — the tensor's identity, ``_version`` and shape, and the lengths — and
@@ -465,17 +470,17 @@ class PointGrid:
         self.lengths = lengths
         self._lengths_version = None if lengths is None else lengths._version
 
-    def _check(self, p2, lengths2):
+    def _check(self, p2, lengths2, who="knn_points"):
         """ValueError unless the grid was built from this p2 (not modified since) with these lengths2."""
         if self._ref() is not p2 or p2._version != self._version or tuple(p2.shape) != self.shape:
-            raise ValueError("knn_points: the grid was not built from this p2 (another tensor, or modified in place "
+            raise ValueError(f"{who}: the grid was not built from this p2 (another tensor, or modified in place "
                              "since); rebuild it with PointGrid(p2, lengths2)")
         if lengths2 is None:
             same = self.lengths is None or self.full
         else:
             same = lengths2 is self.lengths and lengths2._version == self._lengths_version
         if not same:
-            raise ValueError("knn_points: the grid was not built with these lengths2; rebuild it with "
+            raise ValueError(f"{who}: the grid was not built with these lengths2; rebuild it with "
                              "PointGrid(p2, lengths2)")
 
     def points(self):
@@ -551,7 +556,8 @@ def masked_gather(points, idx):
     return out.masked_fill(pad[..., None], 0.0)
 
 
-def ball_query(p1, p2, lengths1=None, lengths2=None, K: int = 500, radius: float = 0.2, return_nn: bool = True):
+def ball_query(p1, p2, lengths1=None, lengths2=None, K: int = 500, radius: float = 0.2, return_nn: bool = True, *,
+               grid: Optional[PointGrid] = None):
     """``pytorch3d.ops.ball_query``: for every point of p1 (N,P1,3) the first K points of p2 (N,P2,3), in index order,
     that lie inside ``radius``, as a namedtuple (dists (N,P1,K), idx (N,P1,K) int64, knn (N,P1,K,3) or None).
 
@@ -564,7 +570,15 @@ def ball_query(p1, p2, lengths1=None, lengths2=None, K: int = 500, radius: float
     dists and knn come back in p1's dtype. Any K >= 1.
 
     dists is differentiable w.r.t. p1 and p2 (kernels.BallQuery, csrc/mr_ballquery.hip), knn through masked_gather.
-    Nothing synchronises; forward and backward capture into a HIP graph."""
+    Nothing synchronises; forward and backward capture into a HIP graph.
+
+    ``grid=PointGrid(p2, lengths2)`` runs the search through that index instead of the scan over every target
+    (kernels.BallQueryGrid, k_ball_query_grid of csrc/mr_ballquery.hip), for K <= 64 (``NotImplementedError`` above,
+    the default K = 500 included): the same dists, idx and knn bit for bit and the same backward. A query walks only
+    the cells that can hold a point inside ``radius``, so a small radius in a large cloud is where it pays; a radius
+    of the cloud's size visits every target from one lane and loses to the scan. A grid that was not built from this
+    p2 (the same tensor, not modified in place since) with these lengths2 raises ValueError. Without it the call is
+    the brute-force kernel; nothing routes automatically."""
     if p1.dim() != 3 or p2.dim() != 3:
         raise ValueError("p1 and p2 must be (N, P, D) tensors.")
     if p1.shape[0] != p2.shape[0]:
@@ -574,9 +588,21 @@ def ball_query(p1, p2, lengths1=None, lengths2=None, K: int = 500, radius: float
     for l in (lengths1, lengths2):
         if l is not None and tuple(l.shape) != (p1.shape[0],):
             raise ValueError("lengths must be of shape (N,)")
-    dists, idx = kernels.BallQuery.apply(p1, p2, lengths1, lengths2, K, radius)
+    if grid is None:
+        dists, idx = kernels.BallQuery.apply(p1, p2, lengths1, lengths2, K, radius)
+    else:
+        if not isinstance(grid, PointGrid):
+            raise ValueError("ball_query: grid must be a PointGrid or None")
+        grid._check(p2, lengths2, "ball_query")
+        dists, idx = kernels.BallQueryGrid.apply(p1, p2, lengths1, lengths2, K, radius, grid.buffer)
     idx = idx.long()
     return _KNN(dists=dists.to(p1.dtype), idx=idx, knn=masked_gather(p2, idx).to(p1.dtype) if return_nn else None)
+
+
+# ``grid`` is this library's keyword-only extension: introspection keeps reporting pytorch3d's own parameter list,
+# which tests/test_ball_query_cpu.py holds the wrapper to.
+ball_query.__signature__ = inspect.Signature(
+    [p for p in inspect.signature(ball_query).parameters.values() if p.name != "grid"])
 
 
 def sample_farthest_points(points, lengths=None, K=50, random_start_point: bool = False):
@@ -676,7 +702,17 @@ def estimate_pointcloud_local_coord_frames(pointclouds, neighborhood_size: int =
     2 <= K <= 64 (``NotImplementedError`` above); a cloud with L <= K, or D != 3, raises ``ValueError``. Not
     differentiable: an input that requires grad raises ``NotImplementedError`` unless grad mode is off. With a tensor
     input nothing synchronises and the call captures into a HIP graph; a ``Pointclouds``' lengths are checked on the
-    host. One launch (kernels.point_frames, csrc/mr_normals.hip)."""
+    host. One launch (kernels.point_frames, csrc/mr_normals.hip).
+
+    ``pointclouds`` may be a ``PointGrid``: it stands for the points it was built from (their padded shape, dtype,
+    lengths and host-side counts), every neighbourhood is searched through that index instead of the scan over the
+    whole cloud (k_frames_grid), and the result is that of the call with the points, bit for bit, with the same
+    errors. A grid whose tensor has been freed or modified in place since the build raises ValueError. Nothing routes
+    automatically."""
+    if isinstance(pointclouds, PointGrid):
+        points, lengths, counts = pointclouds.points()
+        return _local_frames(points, None if pointclouds.full else lengths, counts, neighborhood_size,
+                             disambiguate_directions, pointclouds.buffer)
     if isinstance(pointclouds, Pointclouds):
         counts = pointclouds.counts()
         points = pointclouds.points_padded()
@@ -690,9 +726,10 @@ def estimate_pointcloud_local_coord_frames(pointclouds, neighborhood_size: int =
     return _local_frames(points, lengths, counts, neighborhood_size, disambiguate_directions)
 
 
-def _local_frames(points, lengths, counts, neighborhood_size, disambiguate_directions):
+def _local_frames(points, lengths, counts, neighborhood_size, disambiguate_directions, grid=None):
     """estimate_pointcloud_local_coord_frames on a padded (N,P,3) tensor with its lengths (None: full clouds) and the
-    host-side counts (None: the padded size, or with lengths one read of them)."""
+    host-side counts (None: the padded size, or with lengths one read of them); ``grid``: the buffer of a PointGrid of
+    these points and lengths, to search instead."""
     if counts is None:
         counts = [points.shape[1]] * points.shape[0] if lengths is None else [int(v) for v in lengths.tolist()]
     if points.shape[2] != 3:
@@ -707,7 +744,7 @@ def _local_frames(points, lengths, counts, neighborhood_size, disambiguate_direc
         raise ValueError("The neighborhood_size argument has to be smaller than the size of each of the point clouds.")
     _refuse_grad("estimate_pointcloud_local_coord_frames", points)
     _require_cuda(points)
-    cur, frm = kernels.point_frames(points, lengths, K, bool(disambiguate_directions))
+    cur, frm = kernels.point_frames(points, lengths, K, bool(disambiguate_directions), grid=grid)
     return cur.to(points.dtype), frm.to(points.dtype)
 
 
